@@ -11,7 +11,12 @@ and "capsule_hand" legs. Multi-GPU: one process per GPU, 4096 envs per GPU
 (weak scaling, envs shard with no data-path collective); episode returns are gathered
 over RCCL after the timed region for logging.
 
-Prints ONE JSON line (rank 0); see DESIGN.md "Measurement".
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the
+headline figure and the roofline fraction its own HIP events give. --dump-outputs DIR also
+writes what the last timed step returned (DUMP_BUDGET). --full adds what takes runs or
+gathers of its own: the two other collider sets and the unrefined solve as legs, the CPU
+baseline, the logged episode returns and solver statistics, and the figures quoted from the
+committed profiles. See DESIGN.md "Measurement".
 """
 
 from __future__ import annotations
@@ -50,9 +55,10 @@ HANDS = {
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP32_VECTOR_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: peak FP32 (vector), spec
+DUMP_BUDGET = 64 << 20  # --dump-outputs: bytes in all; above it a seeded sample of the envs
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=50)
@@ -65,12 +71,20 @@ def parse():
                         "colliders, shadow_hand.py:95,144-152, tasks/base.py:101); primitive = the reference's "
                         "primitive_fingertip_collisions=True (palm boxes + capsule distal colliders); authored = "
                         "the all-capsule hand (no reference counterpart)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also time the legs (the other collider sets, the unrefined solve) "
+                        "and the CPU baseline, gather the logged returns and solver statistics, and quote the "
+                        "committed profiles (traffic, wave_time, valu_roofline, qpos_drift)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (obs, reward, discount, step_type) and the state "
+                        "it left (qpos, qvel) as DIR/<name>.npy, float32")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--no-legs", "--no-hull-leg", dest="no_legs", action="store_true",
-                   help="skip timing the same workload with the other two collider sets after the main line")
+                   help="with --full: skip timing the same workload with the other two collider sets after the "
+                        "main line")
     p.add_argument("--cpu-sample-envs", type=int, default=16)
     p.add_argument("--cpu-sample-steps", type=int, default=500)
-    return p.parse_args()
+    return p.parse_args(argv)
 
 
 def load_song(dp, name):
@@ -273,10 +287,28 @@ def stagger_episodes(env, global_start, T):
     env.set_state({"t_idx": t})
 
 
-def timed_rollout(env, actions, steps, warmup, dev, returns, sharding):
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET):
+    """Write ``arrays`` (name -> array with one row per env) as out_dir/<name>.npy in float32.
+    Above ``budget`` bytes in all, the same seeded sample of the envs (sorted, without
+    replacement) is kept of every array and env_index.npy names the rows."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    per_env = sum(a.nbytes // n for a in arrays.values()) + 8  # + the env_index entry
+    if n * per_env > budget:
+        rows = np.sort(np.random.RandomState(12345).choice(n, budget // per_env, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["env_index"] = rows.astype(np.float64)
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(out_dir / f"{k}.npy", a)
+
+
+def timed_rollout(env, actions, steps, warmup, dev, returns, sharding, outputs=None):
     """W untimed steps, then exactly K steps between barrier + device sync on both sides;
     the wall time is the max over ranks. Also the mean per-step device time of env.step from
-    events on the launch stream (None on CPU)."""
+    events on the launch stream (None on CPU). ``outputs`` (a dict) receives what the last
+    timed step returned."""
     import torch
     import torch.distributed as dist
 
@@ -296,11 +328,13 @@ def timed_rollout(env, actions, steps, warmup, dev, returns, sharding):
     for i in range(steps):
         if cuda:
             starts[i].record()
-        _, rew, _, st = env.step(actions[(warmup + i) % pool])
+        obs, rew, disc, st = env.step(actions[(warmup + i) % pool])
         if cuda:
             ends[i].record()
         returns.update(rew, st)
     sync()
+    if outputs is not None and steps > 0:
+        outputs.update(obs=obs, reward=rew, discount=disc, step_type=st)
     if dist_on:
         dist.barrier()
     elapsed = sharding.max_over_ranks(time.perf_counter() - t0, device=dev)
@@ -308,8 +342,8 @@ def timed_rollout(env, actions, steps, warmup, dev, returns, sharding):
     return elapsed, kernel_ms
 
 
-def main():
-    args = parse()
+def main(argv=None):
+    args = parse(argv)
     import torch
     import torch.distributed as dist
 
@@ -332,23 +366,39 @@ def main():
     env.reset()
     stagger_episodes(env, shard.start, env.song.T)
     returns = sharding.EpisodeReturns(N, dev)
-    elapsed, kernel_ms = timed_rollout(env, actions, args.steps, args.warmup, dev, returns, sharding)
-    # logging only: RCCL all-gather of the episode returns over xGMI, after the timed region
-    fin_sum, fin_n, run_sum, n_all = returns.gather()
-    mean_ret = run_sum / n_all
-    # per-env float32 returns of each env's last finished episode, all ranks
-    per_env = sharding.gather_episode_returns(returns, shard, args.envs * world)
-    per_env_done = per_env[~torch.isnan(per_env)]
-    stats = env.solver_stats().cpu().numpy()
+    last = {} if args.dump_outputs else None
+    elapsed, kernel_ms = timed_rollout(env, actions, args.steps, args.warmup, dev, returns, sharding, outputs=last)
+    if last and rank == 0:  # this rank's envs: what the last timed step returned and the state it left
+        state = env.get_state()
+        last.update(qpos=state["qpos"], qvel=state["qvel"])
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in last.items()})
+    logged = None
+    if args.full:
+        # logging only: RCCL all-gather of the episode returns over xGMI, after the timed region
+        fin_sum, fin_n, run_sum, n_all = returns.gather()
+        # per-env float32 returns of each env's last finished episode, all ranks
+        per_env = sharding.gather_episode_returns(returns, shard, args.envs * world)
+        per_env_done = per_env[~torch.isnan(per_env)]
+        stats = env.solver_stats().cpu().numpy()
+        logged = {"mean_return_logged": run_sum / n_all, "episodes_finished": fin_n,
+                  "per_env_returns_gathered": int(per_env.numel()),
+                  "mean_last_episode_return": float(per_env_done.mean()) if per_env_done.numel() else None,
+                  "solver_last_step": {"newton_iterations_per_substep": float(stats[:, 0].mean() / 10.0),
+                                       "contact_cap_substeps": int(stats[:, 1].sum()),
+                                       "newton_cap_substeps": int(stats[:, 2].sum()),
+                                       "max_contact_rows": int(stats[:, 3].max()),
+                                       "coupled_substep_frac": float(stats[:, 4].sum() / (10.0 * stats.shape[0])),
+                                       "bad_pivot_substeps": int(stats[:, 5].sum()),
+                                       "max_coupled_dofs": int(stats[:, 6].max())}}
     obs_dim = env.obs_dim
     total_steps = args.envs * world * args.steps
     value = total_steps / elapsed
     env.close()
     env = None
     legs = {}
-    if not args.no_legs:
+    if args.full and not args.no_legs:
         # the same workload (envs, actions, K, W) with the other collider sets, after the main
-        # timed region; top-level keys of the line (the driver's parsed record keeps them)
+        # timed region; top-level keys of the line
         # and the timed hand without the refining Newton step on coupled substeps (solver_refine=0;
         # TaskConfig's default, timed above, is 1 since round 6: the price of the 1e-4 parity target)
         runs = [(h, h, hand_task(h)) for h in HANDS if h != args.hand]
@@ -369,7 +419,6 @@ def main():
         sha = lib_sha()
         bpe = bytes_per_env_step(obs_dim)
         achieved = bpe * N / (kernel_ms * 1e-3) / 1e9
-        traffic = pmc_traffic(N, args.song, sha, args.hand)
         line = {
             "metric": METRIC,
             "value": value,
@@ -389,28 +438,23 @@ def main():
                                    f"uncapped rows)",
                        "envs_per_gpu": N, "song": args.song, "parallelism": f"dp{world}",
                        "hand": f"{args.hand}: {HANDS[args.hand][2]}",
-                       "mean_return_logged": mean_ret, "episodes_finished": fin_n,
-                       "per_env_returns_gathered": int(per_env.numel()),
-                       "mean_last_episode_return": float(per_env_done.mean()) if per_env_done.numel() else None,
-                       "lib_sha": sha,
-                       "solver_last_step": {"newton_iterations_per_substep": float(stats[:, 0].mean() / 10.0),
-                                            "contact_cap_substeps": int(stats[:, 1].sum()),
-                                            "newton_cap_substeps": int(stats[:, 2].sum()),
-                                            "max_contact_rows": int(stats[:, 3].max()),
-                                            "coupled_substep_frac": float(stats[:, 4].sum() / (10.0 * stats.shape[0])),
-                                            "bad_pivot_substeps": int(stats[:, 5].sum()),
-                                            "max_coupled_dofs": int(stats[:, 6].max())}},
+                       "lib_sha": sha},
+            # of the timed steps themselves (their HIP events); --full adds the profiles' figures
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                         "frac": achieved / HBM_PEAK_GBS,
                          "kernel": HANDS[args.hand][1], "kernel_ms_avg": kernel_ms,
                          "kernel_ms_note": "HIP events around ps_step on the launch stream: order_kernel "
                                            "(counting sort, ~5 us) + pianosim_kernel",
-                         "bytes_per_env_step": bpe, "wave_time": issue_summary(N, args.song, sha, args.hand),
-                         "profile_note": "traffic / wave_time: rocprofv3 PMC passes of this library build "
-                                         "(profiles/pmc_latest.json lib_sha), null when none exists"},
-            "valu_roofline": valu_roofline(args.song, N, kernel_ms),
-            "qpos_drift": drift_summary(sha),
+                         "bytes_per_env_step": bpe},
         }
+        if args.full:
+            line["config"].update(logged)
+            line["roofline"].update(
+                traffic=pmc_traffic(N, args.song, sha, args.hand), wave_time=issue_summary(N, args.song, sha, args.hand),
+                profile_note="traffic / wave_time: rocprofv3 PMC passes of this library build "
+                             "(profiles/pmc_latest.json lib_sha), null when none exists")
+            line["valu_roofline"] = valu_roofline(args.song, N, kernel_ms)
+            line["qpos_drift"] = drift_summary(sha)
         # the other collider sets on the same workload (reference primitive option; all-capsule hand)
         if "primitive" in legs:
             line["primitive_fingertips"] = legs["primitive"]
@@ -420,7 +464,7 @@ def main():
             line["reference_default_hand"] = legs["hull"]
         if "unrefined" in legs:  # TaskConfig(solver_refine=0): no refining step
             line["unrefined_solve"] = legs["unrefined"]
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N=1 figure
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is an N=1 figure
             line["cpu_baseline"] = cpu_baseline(dp, seq, hand_task(args.hand), args.cpu_sample_envs, args.cpu_sample_steps)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -22,7 +22,7 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _rank(rank, world, port, q):
+def _rank(rank, world, port, q, ckpt):
     import importlib
     import sys
     from pathlib import Path
@@ -35,7 +35,7 @@ def _rank(rank, world, port, q):
         ppo = importlib.import_module("diffusion-piano_amd.ppo")
         torch.manual_seed(100 + rank)  # different local init: the broadcast must fix it
         agent = ppo.PPOAgent(64, 45, batch_size=32, ppo_epochs=2, use_wandb=False,
-                             checkpoint_dir=f"/tmp/ppo_dp_{rank}", graphs=True)
+                             checkpoint_dir=f"{ckpt}/ppo_dp_{rank}", graphs=True)
         init = agent.flat.param.detach().cpu().clone()
         rng = np.random.RandomState(rank)
         for _ in range(2):
@@ -51,11 +51,11 @@ def _rank(rank, world, port, q):
         dist.destroy_process_group()
 
 
-def test_two_rank_replicas_stay_identical():
+def test_two_rank_replicas_stay_identical(tmp_path):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_rank, args=(r, 2, port, q)) for r in range(2)]
+    procs = [ctx.Process(target=_rank, args=(r, 2, port, q, str(tmp_path))) for r in range(2)]
     for p in procs:
         p.start()
     res = sorted((q.get(timeout=180) for _ in range(2)), key=lambda t: t[0])

@@ -31,8 +31,7 @@ PIANOSIM_HAND=hull python tools/collect_pmc.py gpurun_out/${P}_trace gpurun_out/
 # the all-capsule hand's kernel trace (its own instantiation) for the record
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${P}_cap_trace -- $B --hand authored --steps 20 > gpurun_out/${P}_cap_trace.log 2>&1 || exit 2
 find gpurun_out/${P}_cap_trace -name "*kernel_stats.csv" -exec cp {} profiles/${P}_capsule_kernel_stats.csv \;
-timeout -k 10 400 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err || exit 1
-cp gpurun_out/bench.json profiles/${P}_bench.json
+timeout -k 10 600 python bench.py --full > profiles/${P}_bench.json 2> $TMPDIR/${P}_bench.err || exit 1
 fi
 if [ "${PART:-all}" != 1 ]; then
 # per-phase cycle split from the -DPS_TIMING build (built on the CPU side beforehand)
