@@ -147,8 +147,28 @@ struct Bufs {
 // LaneDyn words that outlive the constraint solve but are not used by it (the factor of
 // M + hD for the integration, the warm-start and key force terms): parked in the env's row of
 // bufs.park (L2-resident while in use) so their registers are free during the solve
-constexpr int PARK_WORDS = 30;  // 17 around the solve, 7 more inside it (newton_solve); 30 around
-                                // the box / hull collision (the XG kernel, before the solve)
+constexpr int PARK_SUB = 30;  // 17 around the solve, 7 more inside it (newton_solve); 30 around
+                              // the box / hull collision (the XG kernel, before the solve)
+// ... and, on the queue path (pianosim_queue_kernel), what is live across a substep boundary:
+// written at the end of a chunk of substeps, read by the workgroup that runs the env's next one
+enum : int {
+  CW_Q = PARK_SUB, CW_V, CW_KQ, CW_KV = CW_KQ + 2, CW_CTRL = CW_KV + 2, CW_ACTF,
+  CW_ZF, CW_ZL, CW_ZC, CW_CID, CW_ZK,  // the Newton guess (NGuess)
+  CW_SCAL = CW_ZK + 2,                 // wave-uniform words, one per lane (CS_*)
+  PARK_WORDS
+};
+enum : int { CS_SOLVES = 0, CS_CONCAP, CS_CAP, CS_MAXROW, CS_COUPLED, CS_PIV, CS_CDOFS, CS_WARN,
+             CS_GVALID = CS_WARN + PS_NWARN, CS_NOAPPLIED, CS_COUNT };
+static_assert(CS_COUNT <= 64, "one carried scalar per lane");
+constexpr int PS_MAX_CHUNKS = 15;  // a queue item is env * 16 + chunk
+// The carried words are handed from one workgroup to another inside a launch: write-through
+// stores and L1-bypassing loads (global_store / global_load ... sc1), see pianosim_queue_kernel
+__device__ __forceinline__ void st_wt(float* p, float v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ float ld_wt(const float* p) {
+  return __hip_atomic_load(const_cast<float*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
 __device__ __forceinline__ int anc_of(int p0, int p1, int a) {  // a in 1..8
   return (a <= 4 ? (p0 >> (8 * (a - 1))) : (p1 >> (8 * (a - 5)))) & 255;
@@ -1297,33 +1317,46 @@ __device__ __forceinline__ void key_state2(const DevModel* __restrict__ m, Share
 #ifndef PS_WAVES_PER_EU
 #define PS_WAVES_PER_EU 2
 #endif
+#ifndef PS_CHUNKS
+#define PS_CHUNKS 3  // chunks of substeps per env-step on the time-sliced path (pianosim_queue_kernel)
+#endif
 // WPE: resident waves per SIMD the register allocation is built for. 2 (the default): 256 VGPRs,
 // the solve's overflow spilled to scratch; 1: 256 VGPRs + AGPRs, no scratch - chosen by the host
 // when the launch is at most one wave per SIMD anyway (launch() below)
-template <bool XG, int WPE = PS_WAVES_PER_EU>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) pianosim_kernel(const DevModel* __restrict__ m, Song song, Cfg cfg, Bufs bufs,
-                                                      const float* __restrict__ action, const uint8_t* __restrict__ mask,
-                                                      float* __restrict__ obs, float* __restrict__ reward,
-                                                      float* __restrict__ discount, uint8_t* __restrict__ step_type,
-                                                      int mode, int n_envs, const int* __restrict__ order) {
-#ifdef PS_DYN_LDS  // (experiment builds: LDS size set at launch)
-  extern __shared__ __attribute__((aligned(16))) char smem_[];
-  Shared& S = *reinterpret_cast<Shared*>(smem_);
-#else
-  __shared__ Shared S;
-#endif
-  const int e = order ? order[blockIdx.x] : (int)blockIdx.x;
-  const int lane = threadIdx.x;
-  if (e >= n_envs) return;
+//
+// env_step: the control step of env e by one wave, or (Q, the queue path) its chunk `chunk` of
+// `chunks`: substeps [chunk * nsub / chunks, (chunk + 1) * nsub / chunks). A chunk that is not
+// the env's last leaves the state live across the substep boundary in the env's park row (CW_*)
+// and returns true: the caller publishes the continuation; the last chunk also runs the task
+// layer and writes the outputs. Every chunk sets up what it uses (LDS words, lane constants,
+// counters) itself, so any workgroup can run any chunk, and the arithmetic is the monolithic
+// step's: the results do not depend on the chunk count or on who ran which chunk. !Q: the
+// whole step, `chunk` / `chunks` unused (pianosim_kernel).
+template <bool XG, int WPE, bool Q>
+__device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__ m, const Song& song, const Cfg& cfg,
+                                         const Bufs& bufs, const float* __restrict__ action,
+                                         const uint8_t* __restrict__ mask, float* __restrict__ obs,
+                                         float* __restrict__ reward, float* __restrict__ discount,
+                                         uint8_t* __restrict__ step_type, const int mode, const int e, const int lane,
+                                         const int chunk, const int chunks) {
+  const bool first = !Q || chunk == 0;  // the chunk that starts from the env's rows
   float* obs_e = obs + (size_t)e * cfg.obs_dim;
   bool do_reset;
   if (mode == 1) {
-    if (mask && !mask[e]) return;
+    if (mask && !mask[e]) return false;
     do_reset = true;
   } else {
-    do_reset = bufs.last[e] != 0;
+    do_reset = first && bufs.last[e] != 0;  // (an env due for its auto-reset has one chunk only)
   }
   const float* applied = bufs.applied ? bufs.applied + (size_t)e * NV : nullptr;
+  // the carried lane words and wave-uniform scalars of a continued step (Q, chunk > 0)
+  const float* cw = bufs.park + (size_t)e * PARK_WORDS * 64 + lane;
+  int cscal = 0;
+  if (Q && !first) {
+    cscal = __float_as_int(ld_wt(cw + 64 * CW_SCAL));
+    // mj_resetData cleared qfrc_applied in an earlier chunk: none for the rest of the step
+    if (__builtin_amdgcn_readlane(cscal, CS_NOAPPLIED)) applied = nullptr;
+  }
   // randomize_hand_positions (piano_with_shadow_hands.py:491-499): one U(-0.05, 0.05) y shift
   // of both hand roots per episode, drawn at reset (counter-based: seed, env, episode)
   float hand_dy = 0.f;
@@ -1350,6 +1383,14 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
     #pragma unroll
     for (int j = 0; j < 2; j++) { D.kq[j] = D.kv[j] = 0.f; }
     if (lane == 0) S.sustain = 0.f;
+  } else if (Q && !first) {
+    D.q = ld_wt(cw + 64 * CW_Q);
+    D.v = ld_wt(cw + 64 * CW_V);
+#pragma unroll
+    for (int j = 0; j < 2; j++) {
+      D.kq[j] = ld_wt(cw + 64 * (CW_KQ + j));
+      D.kv[j] = ld_wt(cw + 64 * (CW_KV + j));
+    }
   } else {
     int d = lane < NDT ? lane : 0;
     D.q = bufs.qpos[rowoff + NK + d];
@@ -1373,6 +1414,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
     const float av = src >= 0 ? a_e[src] : 0.f;
     ctrl = cfg.canonical ? m->act_clo[a] + (av + 1.f) * 0.5f * (m->act_chi[a] - m->act_clo[a]) : av;
     if (src < 0) ctrl = 0.f;
+    if (Q && !first) ctrl = ld_wt(cw + 64 * CW_CTRL);  // (0 since a physics reset of an earlier chunk)
     const float sv = a_e[m->n_action - 1];
     if (lane == 0) S.sustain = cfg.canonical ? (sv + 1.f) * 0.5f : sv;
   }
@@ -1384,6 +1426,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
   uint64_t tlast = __builtin_amdgcn_s_memtime();
 #endif
   int warn[PS_NWARN] = {0, 0, 0};
+  if (Q && !first) {
+    actf_last = ld_wt(cw + 64 * CW_ACTF);
+    st_solves = __builtin_amdgcn_readlane(cscal, CS_SOLVES);
+    st_concap = __builtin_amdgcn_readlane(cscal, CS_CONCAP);
+    st_cap = __builtin_amdgcn_readlane(cscal, CS_CAP);
+    st_maxrow = __builtin_amdgcn_readlane(cscal, CS_MAXROW);
+    st_coupled = __builtin_amdgcn_readlane(cscal, CS_COUPLED);
+    st_piv = __builtin_amdgcn_readlane(cscal, CS_PIV);
+    st_cdofs = __builtin_amdgcn_readlane(cscal, CS_CDOFS);
+    static_assert(PS_NWARN == 3, "carried warning counters");
+    warn[0] = __builtin_amdgcn_readlane(cscal, CS_WARN);
+    warn[1] = __builtin_amdgcn_readlane(cscal, CS_WARN + 1);
+    warn[2] = __builtin_amdgcn_readlane(cscal, CS_WARN + 2);
+  }
   // mj_resetData (after mj_checkPos / Vel / Acc): qpos = qpos0 (0), qvel, qacc_warmstart,
   // ctrl and qfrc_applied = 0 for the rest of the step
 #define PS_RESET_PHYSICS()                                                              \
@@ -1403,7 +1459,19 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
     guess.cid = -2;
     guess.zk[0] = guess.zk[1] = 0;
     guess.valid = false;
-    for (int s = 0; s < m->nsub; s++) {
+    if (Q && !first) {
+      guess.zf = __float_as_int(ld_wt(cw + 64 * CW_ZF));
+      guess.zl = __float_as_int(ld_wt(cw + 64 * CW_ZL));
+      guess.zc = __float_as_int(ld_wt(cw + 64 * CW_ZC));
+      guess.cid = __float_as_int(ld_wt(cw + 64 * CW_CID));
+      guess.zk[0] = __float_as_int(ld_wt(cw + 64 * CW_ZK));
+      guess.zk[1] = __float_as_int(ld_wt(cw + 64 * (CW_ZK + 1)));
+      guess.valid = __builtin_amdgcn_readlane(cscal, CS_GVALID) != 0;
+    }
+    // (acc_reset is false at every substep boundary: a substep that completes clears it)
+    const int s_begin = Q ? chunk * m->nsub / chunks : 0;
+    const int s_end = Q ? (chunk + 1) * m->nsub / chunks : m->nsub;
+    for (int s = s_begin; s < (Q ? s_end : m->nsub); s++) {
       {  // mj_checkPos, mj_checkVel (mju_isBad: NaN or |x| > 1e10)
         bool bq = lane < NDT && !(fabsf(D.q) <= 1e10f), bv = false;
 #pragma unroll
@@ -1619,6 +1687,34 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
       if (lq == 0) { tacc[9] += 52 + 4 * S.ncon; tacc[10] += S.ncon; }
 #endif
     }
+    if (Q && s_end < m->nsub) {
+      // the step continues in another chunk: everything live across the substep boundary goes
+      // to the env's park row (D.qws / D.kws are outputs of the last substep only; S.sustain
+      // and hand_dy are re-read from the action row / the env's rows by every chunk)
+      float* pw = bufs.park + (size_t)e * PARK_WORDS * 64 + lane;
+      st_wt(pw + 64 * CW_Q, D.q);
+      st_wt(pw + 64 * CW_V, D.v);
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        st_wt(pw + 64 * (CW_KQ + j), D.kq[j]);
+        st_wt(pw + 64 * (CW_KV + j), D.kv[j]);
+      }
+      st_wt(pw + 64 * CW_CTRL, ctrl);
+      st_wt(pw + 64 * CW_ACTF, actf_last);
+      st_wt(pw + 64 * CW_ZF, __int_as_float(guess.zf));
+      st_wt(pw + 64 * CW_ZL, __int_as_float(guess.zl));
+      st_wt(pw + 64 * CW_ZC, __int_as_float(guess.zc));
+      st_wt(pw + 64 * CW_CID, __int_as_float(guess.cid));
+      st_wt(pw + 64 * CW_ZK, __int_as_float(guess.zk[0]));
+      st_wt(pw + 64 * (CW_ZK + 1), __int_as_float(guess.zk[1]));
+      const int sc = lane == CS_SOLVES ? st_solves : lane == CS_CONCAP ? st_concap : lane == CS_CAP ? st_cap
+                   : lane == CS_MAXROW ? st_maxrow : lane == CS_COUPLED ? st_coupled : lane == CS_PIV ? st_piv
+                   : lane == CS_CDOFS ? st_cdofs : lane == CS_WARN ? warn[0] : lane == CS_WARN + 1 ? warn[1]
+                   : lane == CS_WARN + 2 ? warn[2] : lane == CS_GVALID ? (int)guess.valid
+                   : (int)(bufs.applied && !applied);  // CS_NOAPPLIED
+      st_wt(pw + 64 * CW_SCAL, __int_as_float(sc));
+      return true;
+    }
   }
   // ---- mj_step1 at the final state + task layer
   kinematics2<false, XG>(m, S, L, D, lane, hand_dy TPASS);
@@ -1655,7 +1751,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
         step_type[e] = PS_FIRST;
       }
     }
-    return;
+    return false;
   }
   const int t_cur = bufs.t_idx[e];
   const int t_new = t_cur + 1;
@@ -1828,4 +1924,102 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
   if (lane == 0 && g_timing)
     for (int i = 0; i < NPHASE; i++) g_timing[(size_t)e * NPHASE + i] += tacc[i];
 #endif
+  return false;
 }
+
+// One workgroup per env, the whole step (or reset, mode 1) of env order[blockIdx.x].
+template <bool XG, int WPE = PS_WAVES_PER_EU>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) pianosim_kernel(const DevModel* __restrict__ m, Song song, Cfg cfg, Bufs bufs,
+                                                      const float* __restrict__ action, const uint8_t* __restrict__ mask,
+                                                      float* __restrict__ obs, float* __restrict__ reward,
+                                                      float* __restrict__ discount, uint8_t* __restrict__ step_type,
+                                                      int mode, int n_envs, const int* __restrict__ order) {
+#ifdef PS_DYN_LDS  // (experiment builds: LDS size set at launch)
+  extern __shared__ __attribute__((aligned(16))) char smem_[];
+  Shared& S = *reinterpret_cast<Shared*>(smem_);
+#else
+  __shared__ Shared S;
+#endif
+  const int e = order ? order[blockIdx.x] : (int)blockIdx.x;
+  const int lane = threadIdx.x;
+  if (e >= n_envs) return;
+  env_step<XG, WPE, false>(S, m, song, cfg, bufs, action, mask, obs, reward, discount, step_type, mode, e, lane, 0, 1);
+}
+
+enum : int { QC_HEAD = 0, QC_TAIL = 32, QC_WORDS = 64 };  // (the two counters on lines of their own)
+#ifndef PS_TIMING  // (the timing build's per-env accumulators are those of whole steps)
+// The step of a launch of more envs than resident wave slots, time-sliced: the grid is the
+// resident slots, and every workgroup takes (env, chunk) items off a FIFO in global memory
+// until it finds none. order_kernel has put the n chunk-0 items at the front (queue[0..n),
+// longest expected first), set queue[n..cap) to QE_NONE (unpublished) and ctr[QC_HEAD] = the
+// grid (workgroup b starts with item b), ctr[QC_TAIL] = n. A workgroup that finishes a chunk
+// with substeps left reserves the slot ctr[QC_TAIL]++ and publishes the env's next chunk there;
+// each env has at most `chunks` items, so cap = n * chunks slots always suffice.
+//
+// No workgroup ever waits for another, and no step of the protocol is retried. A pop takes the
+// ticket t = ctr[QC_HEAD]++ and EXCHANGES queue[t] with QE_LEFT: it gets the item, or (QE_NONE:
+// the queue is empty, t is unpublished or never will be; t >= cap likewise) the workgroup
+// EXITS. A publisher exchanges its item into its slot: if it gets QE_LEFT back, the ticket's
+// holder has left and nobody else will ever read the slot, so the publisher runs the item
+// itself. The exchange decides every slot for exactly one of the two sides, so no item is
+// orphaned and none runs twice; a workgroup leaves only when everything published so far is
+// taken, and what is published later stays with, or behind, a workgroup that is still running.
+// (A compare-and-swap pop of the head - read head, read entry, swap - was measured first: under
+// 2048 workgroups it succeeds once per round trip, 2-4 us per item, and the 4096-env step took
+// 22 ms against 5.5 ms.)
+//
+// Hand-off (per-XCD L2s are not coherent with each other, a CU's L1 is not refreshed by other
+// CUs' stores): the carried words are stored write-through (st_wt), the wave drains its stores,
+// then lane 0 exchanges the item in; the consumer's lane 0 gets the item by its exchange, then
+// one agent-scope acquire (the L1 invalidate) and the wave barrier come before the env's rows
+// are read, the carried words again past L1 (ld_wt). No agent-scope release fence: it writes
+// back the XCD's whole L2, which here holds every resident wave's scratch - measured, a release
+// per chunk boundary and per pop made the 4096-env step 16x slower (89 ms). Nothing else is
+// handed over inside a launch: the env's other rows are read by its first chunk and written by
+// its last.
+enum : int { QE_NONE = -1, QE_LEFT = -2 };
+template <bool XG>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PS_WAVES_PER_EU))) pianosim_queue_kernel(
+    const DevModel* __restrict__ m, Song song, Cfg cfg, Bufs bufs, const float* __restrict__ action,
+    float* __restrict__ obs, float* __restrict__ reward, float* __restrict__ discount, uint8_t* __restrict__ step_type,
+    int n_envs, int* queue, int* ctr, int cap, int chunks) {
+  __shared__ Shared S;
+  const int lane = threadIdx.x;
+  // the first item: queue[blockIdx.x] (grid <= n_envs; written by order_kernel)
+  int own = queue[blockIdx.x];  // an item this workgroup already holds, or QE_NONE: pop one
+  for (;;) {
+    int item = own;
+    if (own < 0 && lane == 0) {
+      const int t = __hip_atomic_fetch_add(&ctr[QC_HEAD], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (t < cap) item = __hip_atomic_exchange(&queue[t], QE_LEFT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the acquire's invalidate has completed)
+    item = __builtin_amdgcn_readfirstlane(item);
+    // opaque per item: nothing derived from the env is hoisted across items
+    asm volatile("" : "+s"(item));
+    wsync();
+    if (item < 0) return;
+    const int e = item >> 4, chunk = item & 15;
+    if (e >= n_envs) return;  // (never: order_kernel and the continuations write valid items only)
+    const bool more = env_step<XG, PS_WAVES_PER_EU, true>(S, m, song, cfg, bufs, action, nullptr, obs, reward, discount,
+                                                          step_type, 0, e, lane, chunk, chunks);
+    // (uniform: the whole wave returns the same) every lane's write-through stores have completed
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wsync();
+    own = QE_NONE;
+    if (more) {
+      const int next = (e << 4) | (chunk + 1);
+      int old = QE_NONE;
+      if (lane == 0) {
+        const int slot = __hip_atomic_fetch_add(&ctr[QC_TAIL], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // (slot < cap always: at most `chunks` items per env; past it the item stays here)
+        old = slot < cap ? __hip_atomic_exchange(&queue[slot], next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                         : (int)QE_LEFT;
+      }
+      if (__builtin_amdgcn_readfirstlane(old) == QE_LEFT) own = next;
+    }
+    wsync();  // the next item's LDS writes come after this chunk's reads
+  }
+}
+#endif

@@ -56,11 +56,17 @@ struct ps_env {
   int* episode;             // resets so far per env (the draw counter)
   int* stats;               // [N][PS_NSTATS] solver / cap counters of the last step
   int* warnings;            // [N][PS_NWARN] physics warnings since create
-  float* park;              // [N][PARK_WORDS][64] kernel scratch (lane state around the Newton solve)
+  float* park;              // [N][PARK_WORDS][64] kernel scratch (lane state around the Newton solve,
+                            // and between the chunks of a time-sliced step)
   uint64_t seed;
   bool has_x;               // box / hull colliders: the pianosim_kernel<true> instantiation
   int wave_slots;           // SIMDs of the device: a step launch of at most this many envs runs one
                             // wave per SIMD and takes the one-wave (no-scratch) instantiation
+  // the time-sliced step (pianosim_queue_kernel): chunks per env-step (0: never), the grid
+  // (resident wave slots, or PIANOSIM_STEP_GRID), whether PIANOSIM_CHUNKS forces it for every n
+  int chunks, step_grid;
+  bool chunks_forced;
+  int *queue, *qctr;        // [n * chunks] items, [QC_WORDS] head / tail counters
   Contact* con_out;         // [N][MAXCON] contact lists of the last step (ps_record_contacts)
 };
 
@@ -628,6 +634,25 @@ int ps_create(const ps_model_desc* model, const ps_song_desc* song, const ps_tas
     E->wave_slots = 4 * cus;  // 4 SIMDs per CDNA compute unit
     const char* w = getenv("PIANOSIM_ONE_WAVE_MAX");  // (A/B runs: the threshold; 0 never)
     if (w) E->wave_slots = atoi(w);
+    // PIANOSIM_CHUNKS (A/B runs, tests): 0 or 1 = every step monolithic; k >= 2 = every step
+    // launch time-sliced in k chunks. Unset: PS_CHUNKS chunks where launch() takes that path.
+    // PIANOSIM_STEP_GRID: workgroups of the time-sliced launch (tests: items cross workgroups
+    // at small n); default the resident slots of the two-wave build.
+    const char* c = getenv("PIANOSIM_CHUNKS");
+    E->chunks_forced = c != nullptr;
+    E->chunks = c ? atoi(c) : PS_CHUNKS;
+    if (E->chunks > PS_MAX_CHUNKS) E->chunks = PS_MAX_CHUNKS;
+    if (E->chunks > model->n_substeps) E->chunks = model->n_substeps;
+    if (E->chunks < 2) E->chunks = 0;
+    const char* g = getenv("PIANOSIM_STEP_GRID");
+    E->step_grid = g && atoi(g) > 0 ? atoi(g) : PS_WAVES_PER_EU * 4 * cus;
+#ifdef PS_TIMING
+    E->chunks = 0;  // (the timing build has no queue kernel)
+#endif
+    if (E->chunks) {
+      HIPCHK(hipMalloc(&E->queue, sizeof(int) * N * E->chunks));
+      HIPCHK(hipMalloc(&E->qctr, sizeof(int) * QC_WORDS));
+    }
   }
   *out = E;
   return 0;
@@ -645,15 +670,22 @@ void ps_destroy(ps_env* E) {
   hipFree(E->mus_acc); hipFree(E->mus_ep); hipFree(E->mus_cnt); hipFree(E->order);
   hipFree(E->hand_dy); hipFree(E->episode); hipFree(E->stats); hipFree(E->warnings); hipFree(E->park);
   if (E->con_out) hipFree(E->con_out);
+  if (E->queue) hipFree(E->queue);
+  if (E->qctr) hipFree(E->qctr);
   delete E;
 }
 
 // Dispatch order of a step launch: envs by the cost of their previous step, descending -
 // the Newton iterations its substeps took (PS_STAT_SOLVES: each is a Hessian assembly,
-// factorization and line search) - envs about to auto-reset (no physics this step) last. Workgroups are dispatched in blockIdx order, so the expensive envs start in
-// the first wave of workgroups and the cheap ones fill the slots freed late (longest-
-// processing-time-first): the launch's tail is shorter. Each env's result is independent of
-// the order.
+// factorization and line search) - envs about to auto-reset (no physics this step) last.
+// Workgroups are dispatched in blockIdx order, so the expensive envs start in the first wave
+// of workgroups and the cheap ones fill the slots freed late (longest-processing-time-first):
+// the launch's tail is shorter. Each env's result is independent of the order.
+// With a queue (the time-sliced step, pianosim_queue_kernel) the order is written as the
+// queue's first n items (env << 4 | chunk 0) instead - in env order when `sorted` is false -
+// the other entries are set to -1 (unpublished) and the counters to head = the step's grid
+// (workgroup b starts with item b), tail = n: launched before every such step, so the queue
+// is reset in stream order (and under graph capture).
 #ifdef PS_DYN_LDS
 #define PS_LAUNCH_LDS PS_DYN_LDS
 #else
@@ -663,8 +695,21 @@ constexpr int ORDER_THREADS = 1024;
 constexpr int ORDER_BUCKETS = 130;  // 0: resets, 1 + min(Newton iterations of the last step, 128)
 __global__ void __launch_bounds__(ORDER_THREADS) order_kernel(const int* __restrict__ stats,
                                                               const uint8_t* __restrict__ last,
-                                                              int* __restrict__ order, int n) {
+                                                              int* __restrict__ order, int n, int* __restrict__ queue,
+                                                              int* __restrict__ qctr, int qcap, int qhead,
+                                                              bool sorted) {
   __shared__ int hist[ORDER_BUCKETS], base[ORDER_BUCKETS];
+  if (queue) {
+    for (int i = n + threadIdx.x; i < qcap; i += blockDim.x) queue[i] = -1;
+    if (threadIdx.x == 0) {
+      qctr[QC_HEAD] = qhead;
+      qctr[QC_TAIL] = n;
+    }
+    if (!sorted) {
+      for (int e = threadIdx.x; e < n; e += blockDim.x) queue[e] = e << 4;
+      return;
+    }
+  }
   if (threadIdx.x < ORDER_BUCKETS) hist[threadIdx.x] = 0;
   __syncthreads();
   for (int e = threadIdx.x; e < n; e += blockDim.x) {
@@ -674,7 +719,7 @@ __global__ void __launch_bounds__(ORDER_THREADS) order_kernel(const int* __restr
   __syncthreads();
   if (threadIdx.x == 0) {
     int acc = 0;
-    for (int b = ORDER_BUCKETS - 1; b >= 0; b--) {  // most rows first, resets last
+    for (int b = ORDER_BUCKETS - 1; b >= 0; b--) {  // most iterations first, resets last
       base[b] = acc;
       acc += hist[b];
     }
@@ -682,7 +727,9 @@ __global__ void __launch_bounds__(ORDER_THREADS) order_kernel(const int* __restr
   __syncthreads();
   for (int e = threadIdx.x; e < n; e += blockDim.x) {
     const int b = last[e] ? 0 : 1 + min(max(stats[(size_t)e * PS_NSTATS + PS_STAT_SOLVES], 0), 128);
-    order[atomicAdd(&base[b], 1)] = e;
+    const int pos = atomicAdd(&base[b], 1);
+    if (queue) queue[pos] = e << 4;
+    else order[pos] = e;
   }
 }
 
@@ -697,10 +744,29 @@ static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask,
   Bufs b{E->qpos, E->qvel, E->qws, E->ctrl, E->sustain, E->t_idx, E->last,
          E->applied_on ? E->applied : nullptr, E->terms, E->tips, E->ncon, E->mus_acc, E->mus_ep, E->mus_cnt,
          E->hand_dy, E->episode, E->stats, E->con_out, E->warnings, E->park};
+  // the time-sliced step: a launch of more envs than resident slots (below that every env has a
+  // slot of its own from the start and there is no second round to balance), or every step
+  // when PIANOSIM_CHUNKS says so
+  const bool sliced = mode == 0 && E->chunks >= 2 && (E->chunks_forced || E->n > E->step_grid);
+  if (sliced) {
+    const int cap = E->n * E->chunks, grid = E->n < E->step_grid ? E->n : E->step_grid;
+    hipLaunchKernelGGL(order_kernel, dim3(1), dim3(ORDER_THREADS), 0, (hipStream_t)stream, E->stats, E->last, E->order,
+                       E->n, E->queue, E->qctr, cap, grid, E->ordered);
+    HIPCHK(hipGetLastError());
+#ifndef PS_TIMING
+#define PS_LAUNCH_Q(XG)                                                                                           \
+  hipLaunchKernelGGL((pianosim_queue_kernel<XG>), dim3(grid), dim3(64), 0, (hipStream_t)stream, E->d_model, song, \
+                     cfg, b, action, obs, reward, discount, step_type, E->n, E->queue, E->qctr, cap, E->chunks)
+    if (E->has_x) PS_LAUNCH_Q(true); else PS_LAUNCH_Q(false);
+#undef PS_LAUNCH_Q
+#endif
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   const int* order = nullptr;
   if (mode == 0 && E->ordered && E->n >= 2048) {  // below one wave of workgroups there is no tail to balance
     hipLaunchKernelGGL(order_kernel, dim3(1), dim3(ORDER_THREADS), 0, (hipStream_t)stream, E->stats, E->last, E->order,
-                       E->n);
+                       E->n, (int*)nullptr, (int*)nullptr, 0, 0, true);
     HIPCHK(hipGetLastError());
     order = E->order;
   }
