@@ -4,10 +4,11 @@ Import with ``importlib.import_module("diffusion-piano_amd")`` (the directory na
 package name required by the build layout).
 """
 
-from . import abi, music, model, mjcf, evaluation  # noqa: F401
+from . import abi, music, model, mjcf, evaluation, variations  # noqa: F401
 from .envs import (  # noqa: F401
     Array, BatchedPianoEnv, BoundedArray, DEBUG, Environment, PhysicsError, StepType, TaskConfig, TimeStep,
     VectorizedPianoEnv, compile_task, load, obs_layout,
 )
 from .evaluation import MidiEvaluationWrapper  # noqa: F401,E402
 from ._lib import PianosimError  # noqa: F401,E402
+from .variations import MidiOctaveShift, MidiPitchShift, MidiSelect, MidiTemporalStretch  # noqa: F401,E402

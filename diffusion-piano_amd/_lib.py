@@ -17,7 +17,8 @@ EXPORTS = (
     "ps_reset", "ps_step", "ps_get_state", "ps_set_state", "ps_set_applied", "ps_reward_terms",
     "ps_fingertips", "ps_contact_count", "ps_musical_metrics", "ps_solver_stats", "ps_get_hand_offset",
     "ps_set_hand_offset", "ps_record_contacts", "ps_contacts", "ps_set_env_offset", "ps_warnings",
-    "ps_env_obs_dim", "ps_env_action_dim", "ps_episode_returns",
+    "ps_env_obs_dim", "ps_env_action_dim", "ps_episode_returns", "ps_set_augmentations", "ps_get_augmentation",
+    "ps_set_augmentation", "ps_get_song_tables",
 )
 
 # Every entry point declared in include/pianorl.h.
@@ -75,7 +76,8 @@ def load() -> C.CDLL:
         L.ps_episode_returns.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     if hasattr(L, "ps_set_env_offset"):
         L.ps_set_env_offset.argtypes = [vp, C.c_int64]
-    for name, argc in (("ps_solver_stats", 3), ("ps_get_hand_offset", 4), ("ps_set_hand_offset", 3),
+    for name, argc in (("ps_set_augmentations", 2), ("ps_get_augmentation", 7), ("ps_set_augmentation", 5),
+                       ("ps_get_song_tables", 6), ("ps_solver_stats", 3), ("ps_get_hand_offset", 4), ("ps_set_hand_offset", 3),
                        ("ps_contacts", 3), ("ps_warnings", 3), ("ps_env_obs_dim", 1), ("ps_env_action_dim", 1)):
         if hasattr(L, name):  # (absent from older builds loaded for A/B runs via PIANOSIM_LIB)
             getattr(L, name).argtypes = [vp] * argc
@@ -139,7 +141,8 @@ def load_rl() -> C.CDLL:
 SONG_LIB_PATH = Path(os.environ.get("PIANOSONG_LIB", HERE / "libpianosong.so"))
 # Every entry point declared in include/pianosong.h.
 SONG_EXPORTS = ("pss_last_error", "pss_version", "pss_parse_midi", "pss_from_notes", "pss_free", "pss_info",
-                "pss_get", "pss_add_fingering", "pss_trim_silence", "pss_song_tables")
+                "pss_get", "pss_add_fingering", "pss_trim_silence", "pss_song_tables", "pss_stretch", "pss_transpose",
+                "pss_flatten", "pss_build_tables", "pss_draw_augmentation")
 _song = None
 
 
@@ -164,6 +167,12 @@ def load_song() -> C.CDLL:
     L.pss_add_fingering.argtypes = [vp, C.c_char_p]
     L.pss_trim_silence.argtypes = [vp]
     L.pss_song_tables.argtypes = [vp, f64, f64, i32, i32, vp, vp, vp, vp, C.POINTER(i32)]
+    L.pss_stretch.argtypes = [vp, f64]
+    L.pss_transpose.argtypes = [vp, i32]
+    L.pss_flatten.argtypes = [vp, vp, vp, C.POINTER(i32), C.POINTER(f64), vp]
+    L.pss_build_tables.argtypes = [vp, f64, i32, f64, f64, i32, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.pss_draw_augmentation.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, vp, i32, vp, i32, C.POINTER(i32),
+                                        C.POINTER(f64), C.POINTER(i32)]
     for name in SONG_EXPORTS[2:]:
         if name != "pss_free":
             getattr(L, name).restype = i32

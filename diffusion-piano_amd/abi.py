@@ -126,6 +126,34 @@ class TaskCfg(C.Structure):
             self.struct_size = C.sizeof(TaskCfg)
 
 
+class AugSong(C.Structure):
+    """ps_aug_song (the layout of pss_flat_song / music.FlatSong)."""
+    _fields_ = [("notes", C.c_void_p), ("ccs", C.c_void_p), ("n_notes", i32), ("n_cc", i32), ("total_time", d),
+                ("pitch_mask", C.c_uint32 * 4)]
+
+
+class Variation(C.Structure):
+    """ps_variation: kind VAR_SELECT / VAR_STRETCH / VAR_PITCH / VAR_OCTAVE."""
+    _fields_ = [("kind", i32), ("prob", d), ("range", d)]
+
+
+VAR_SELECT, VAR_STRETCH, VAR_PITCH, VAR_OCTAVE = 1, 2, 3, 4
+MAX_VARIATIONS = 4
+AUG_ROW_BYTES = 4 * (NKEY + 1) + 4 * (1 + 2 * MAX_NOTES)  # one row of one env's song tables: 488
+
+
+class AugmentDesc(C.Structure):
+    """ps_augment_desc; struct_size is set to the struct's size."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_songs", i32), ("songs", C.POINTER(AugSong)), ("n_variations", i32),
+                ("variations", C.POINTER(Variation)), ("dt", d), ("initial_buffer_time", d), ("T_cap", i32),
+                ("max_bytes", C.c_uint64)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if "struct_size" not in kw:
+            self.struct_size = C.sizeof(AugmentDesc)
+
+
 SOLVER_EXACT = SOLVER_NEWTON = 1
 HAND_POSITION_OFFSET = 0.05  # piano_with_shadow_hands.py:46
 

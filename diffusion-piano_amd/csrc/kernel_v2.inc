@@ -115,7 +115,19 @@ struct Song {
   const int* count;
   const int* keys;
   const int* fingers;
+  // per-episode MIDI augmentations (augment.inc): env e has rows [e * stride, e * stride + T_env[e])
+  // of the four tables, rebuilt by song_build_kernel before its episode. A plain handle: stride 0,
+  // T_env null, every env reads the one song above.
+  int stride;
+  const int* T_env;
 };
+// env e's song (wave-uniform)
+__device__ __forceinline__ Song song_of(const Song& s, const int e) {
+  if (!s.T_env) return s;
+  const size_t row = (size_t)e * (size_t)s.stride;
+  return Song{s.T_env[e], s.goal + row * (NK + 1), s.count + row, s.keys + row * PS_MAX_NOTES,
+              s.fingers + row * PS_MAX_NOTES, s.stride, s.T_env};
+}
 
 struct Cfg {
   int lookahead, fingering, forearm, wrong_press, newton_cap, maxcon, obs_dim, canonical;
@@ -1333,13 +1345,14 @@ __device__ __forceinline__ void key_state2(const DevModel* __restrict__ m, Share
 // step's: the results do not depend on the chunk count or on who ran which chunk. !Q: the
 // whole step, `chunk` / `chunks` unused (pianosim_kernel).
 template <bool XG, int WPE, bool Q>
-__device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__ m, const Song& song, const Cfg& cfg,
+__device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__ m, const Song& songs, const Cfg& cfg,
                                          const Bufs& bufs, const float* __restrict__ action,
                                          const uint8_t* __restrict__ mask, float* __restrict__ obs,
                                          float* __restrict__ reward, float* __restrict__ discount,
                                          uint8_t* __restrict__ step_type, const int mode, const int e, const int lane,
                                          const int chunk, const int chunks) {
   const bool first = !Q || chunk == 0;  // the chunk that starts from the env's rows
+  const Song song = song_of(songs, e);
   float* obs_e = obs + (size_t)e * cfg.obs_dim;
   bool do_reset;
   if (mode == 1) {

@@ -22,6 +22,7 @@
 using namespace ps;
 
 #include "kernel_v2.inc"
+#include "augment.inc"
 
 // ------------------------------------------------------------------ host side
 static thread_local std::string g_err;
@@ -68,6 +69,12 @@ struct ps_env {
   bool chunks_forced;
   int *queue, *qctr;        // [n * chunks] items, [QC_WORDS] head / tail counters
   Contact* con_out;         // [N][MAXCON] contact lists of the last step (ps_record_contacts)
+  // per-episode MIDI augmentations (ps_set_augmentations): the device bank and per-env tables,
+  // the builder's dynamic LDS bytes; every device allocation of it in aug_mem
+  bool aug_on;
+  AugDev aug;
+  size_t aug_lds;
+  std::vector<void*> aug_mem;
 };
 
 // Every entry point that touches device memory or launches binds the handle's device for its
@@ -526,6 +533,22 @@ static int build_dev_model(const ps_model_desc* d, DevModel* m) {
   return 0;
 }
 
+static void free_aug(ps_env* E) {
+  for (void* p : E->aug_mem) (void)hipFree(p);
+  E->aug_mem.clear();
+  E->aug_on = false;
+}
+
+// the builder of an augmented handle, before the step / reset kernel that reads its rows
+static int launch_builder(ps_env* E, int mode, const uint8_t* mask, const int* f_song, const double* f_factor,
+                          const int* f_shift, void* stream) {
+  hipLaunchKernelGGL(song_build_kernel, dim3(E->n), dim3(64), E->aug_lds, (hipStream_t)stream, E->aug, mode, mask,
+                     E->last, E->episode, (uint32_t)E->seed, (uint32_t)(E->seed >> 32), (uint32_t)E->env_offset, E->n,
+                     f_song, f_factor, f_shift);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 extern "C" {
 
 const char* ps_last_error(void) { return g_err.c_str(); }
@@ -672,6 +695,7 @@ void ps_destroy(ps_env* E) {
   if (E->con_out) hipFree(E->con_out);
   if (E->queue) hipFree(E->queue);
   if (E->qctr) hipFree(E->qctr);
+  free_aug(E);
   delete E;
 }
 
@@ -735,7 +759,11 @@ __global__ void __launch_bounds__(ORDER_THREADS) order_kernel(const int* __restr
 
 static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask, float* obs, float* reward,
                   float* discount, uint8_t* step_type, void* stream) {
-  Song song{E->T, E->d_goal, E->d_count, E->d_keys, E->d_fingers};
+  Song song{E->T, E->d_goal, E->d_count, E->d_keys, E->d_fingers, 0, nullptr};
+  if (E->aug_on) {
+    song = Song{E->T, E->aug.goal, E->aug.count, E->aug.keys, E->aug.fingers, E->aug.T_cap, E->aug.T};
+    if (launch_builder(E, mode == 1 ? AUG_RESET : AUG_STEP, mask, nullptr, nullptr, nullptr, stream)) return -1;
+  }
   Cfg cfg{E->cfg.n_steps_lookahead, E->cfg.fingering_reward, E->cfg.forearm_reward, E->cfg.wrong_press_termination,
           E->cfg.solver_iterations, E->cfg.max_contacts, E->obs_dim, E->cfg.canonical_actions,
           (float)E->cfg.energy_penalty_coef, E->cfg.randomize_hand_positions != 0,
@@ -944,6 +972,158 @@ int ps_warnings(ps_env* E, int32_t* warnings, void* stream) {
   GUARD(E);
   HIPCHK(hipMemcpyAsync(warnings, E->warnings, sizeof(int) * E->n * PS_NWARN, hipMemcpyDeviceToDevice,
                         (hipStream_t)stream));
+  return 0;
+}
+
+static_assert(sizeof(ps_aug_song) == sizeof(psb::Song) && sizeof(ps_variation) == sizeof(psb::Var),
+              "pianosim.h mirrors song_build.h");
+#define AUG_ALLOC(ptr, bytes)                         \
+  do {                                                \
+    void* p_ = nullptr;                               \
+    HIPCHK(hipMalloc(&p_, (bytes)));                  \
+    E->aug_mem.push_back(p_);                         \
+    (ptr) = reinterpret_cast<decltype(ptr)>(p_);      \
+  } while (0)
+int ps_set_augmentations(ps_env* E, const ps_augment_desc* d) {
+  if (!E) return fail("null env");
+  GUARD(E);
+  HIPCHK(hipDeviceSynchronize());  // (init-time: nothing of the old bank is in flight)
+  free_aug(E);
+  if (!d) return 0;
+  if (d->struct_size != PS_AUGMENT_DESC_SIZE)
+    return fail("ps_augment_desc.struct_size != sizeof(ps_augment_desc): rebuild against include/pianosim.h");
+  if (d->n_songs < 1 || !d->songs) return fail("ps_set_augmentations: an empty bank");
+  if (d->n_variations < 0 || d->n_variations > PS_MAX_VARIATIONS || (d->n_variations && !d->variations))
+    return fail("ps_set_augmentations: 0 .. PS_MAX_VARIATIONS variations");
+  if (!(d->dt > 0) || d->initial_buffer_time < 0) return fail("ps_set_augmentations: bad dt / initial_buffer_time");
+  const long nbuf = (long)nearbyint(d->initial_buffer_time / d->dt);
+  if (d->T_cap <= nbuf || d->T_cap > (1 << 20)) return fail("ps_set_augmentations: T_cap out of range");
+  for (int i = 0; i < d->n_variations; i++) {
+    const ps_variation& v = d->variations[i];
+    if (v.kind < PS_VAR_SELECT || v.kind > PS_VAR_OCTAVE) return fail("ps_set_augmentations: unknown variation kind");
+    if (!(v.range >= 0) || (v.kind == PS_VAR_STRETCH && !(v.range < 1)) || v.range > 1e6)
+      return fail("ps_set_augmentations: variation range out of bounds");
+  }
+  const long F_cap = d->T_cap - nbuf;
+  const size_t lds = (size_t)F_cap * (psb::NKEYS + 1);
+  if (lds > 65536)
+    return fail("ps_set_augmentations: the builder's roll of " + std::to_string(F_cap) + " frames needs " +
+                std::to_string(lds) + " B of LDS; a workgroup may take 65536");
+  const size_t N = (size_t)E->n, rows = N * (size_t)d->T_cap;
+  const size_t row_bytes = sizeof(float) * (NK + 1) + sizeof(int) * (1 + 2 * PS_MAX_NOTES);
+  if (d->max_bytes && rows * row_bytes > d->max_bytes)
+    return fail("ps_set_augmentations: the per-env song tables need " + std::to_string(rows * row_bytes) + " B (" +
+                std::to_string(E->n) + " envs x " + std::to_string(d->T_cap) + " rows x " +
+                std::to_string(row_bytes) + " B), over the budget of " + std::to_string(d->max_bytes) + " B");
+  // every song as given has to fit: the builder falls back to it
+  const double fps = 1.0 / d->dt;
+  {
+    std::vector<uint32_t> roll((size_t)F_cap * psb::ROW_WORDS);
+    std::vector<uint8_t> sus((size_t)F_cap);
+    for (int i = 0; i < d->n_songs; i++) {
+      const ps_aug_song& g = d->songs[i];
+      if (g.n_notes < 1 || !g.notes || g.n_cc < 0 || (g.n_cc && !g.ccs))
+        return fail("ps_set_augmentations: song " + std::to_string(i) + " is empty");
+      psb::Song h;
+      memcpy(&h, &g, sizeof(h));
+      if (psb::build_roll(h, 1.0, 0, fps, F_cap, roll.data(), sus.data(), 0, 1) < 0)
+        return fail("ps_set_augmentations: song " + std::to_string(i) + " as given does not fit " +
+                    std::to_string(d->T_cap) + " rows of at most " + std::to_string(PS_MAX_NOTES) + " keys");
+    }
+  }
+  AugDev a{};
+  a.n_songs = d->n_songs;
+  a.n_vars = d->n_variations;
+  a.fps = fps;
+  a.nbuf = (int)nbuf;
+  a.T_cap = d->T_cap;
+  std::vector<psb::Song> bank(d->n_songs);
+  for (int i = 0; i < d->n_songs; i++) {
+    const ps_aug_song& g = d->songs[i];
+    memcpy(&bank[i], &g, sizeof(psb::Song));
+    double *dn = nullptr, *dc = nullptr;
+    AUG_ALLOC(dn, sizeof(double) * 4 * g.n_notes);
+    HIPCHK(hipMemcpy(dn, g.notes, sizeof(double) * 4 * g.n_notes, hipMemcpyHostToDevice));
+    if (g.n_cc) {
+      AUG_ALLOC(dc, sizeof(double) * 2 * g.n_cc);
+      HIPCHK(hipMemcpy(dc, g.ccs, sizeof(double) * 2 * g.n_cc, hipMemcpyHostToDevice));
+    }
+    bank[i].notes = dn;
+    bank[i].ccs = dc;
+  }
+  psb::Song* dbank = nullptr;
+  AUG_ALLOC(dbank, sizeof(psb::Song) * d->n_songs);
+  HIPCHK(hipMemcpy(dbank, bank.data(), sizeof(psb::Song) * d->n_songs, hipMemcpyHostToDevice));
+  a.bank = dbank;
+  psb::Var* dvars = nullptr;
+  AUG_ALLOC(dvars, sizeof(psb::Var) * (d->n_variations + 1));
+  if (d->n_variations)
+    HIPCHK(hipMemcpy(dvars, d->variations, sizeof(psb::Var) * d->n_variations, hipMemcpyHostToDevice));
+  a.vars = dvars;
+  AUG_ALLOC(a.song, sizeof(int) * N);
+  AUG_ALLOC(a.factor, sizeof(double) * N);
+  AUG_ALLOC(a.shift, sizeof(int) * N);
+  AUG_ALLOC(a.T, sizeof(int) * N);
+  AUG_ALLOC(a.fallbacks, sizeof(int) * N);
+  AUG_ALLOC(a.goal, sizeof(float) * rows * (NK + 1));
+  AUG_ALLOC(a.count, sizeof(int) * rows);
+  AUG_ALLOC(a.keys, sizeof(int) * rows * PS_MAX_NOTES);
+  AUG_ALLOC(a.fingers, sizeof(int) * rows * PS_MAX_NOTES);
+  HIPCHK(hipMemset(a.goal, 0, sizeof(float) * rows * (NK + 1)));
+  HIPCHK(hipMemset(a.count, 0, sizeof(int) * rows));
+  HIPCHK(hipMemset(a.keys, 0xff, sizeof(int) * rows * PS_MAX_NOTES));
+  HIPCHK(hipMemset(a.fingers, 0xff, sizeof(int) * rows * PS_MAX_NOTES));
+  HIPCHK(hipMemset(a.song, 0, sizeof(int) * N));
+  HIPCHK(hipMemset(a.shift, 0, sizeof(int) * N));
+  HIPCHK(hipMemset(a.T, 0, sizeof(int) * N));
+  {
+    std::vector<double> one(N, 1.0);
+    HIPCHK(hipMemcpy(a.factor, one.data(), sizeof(double) * N, hipMemcpyHostToDevice));
+  }
+  E->aug = a;
+  E->aug_lds = lds;
+  // every env starts with song 0 as given (a step before the first reset plays it, as on a plain handle)
+  if (launch_builder(E, AUG_FORCED, nullptr, a.song, a.factor, a.shift, nullptr)) return -1;
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemset(a.fallbacks, 0, sizeof(int) * N));
+  E->aug_on = true;
+  return 0;
+}
+#undef AUG_ALLOC
+
+int ps_get_augmentation(ps_env* E, int32_t* song, double* factor, int32_t* shift, int32_t* T, int32_t* fallbacks,
+                        void* stream) {
+  if (!E) return fail("null env");
+  GUARD(E);
+  if (!E->aug_on) return fail("the handle has no augmentations (ps_set_augmentations)");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t N = E->n;
+  if (song) HIPCHK(hipMemcpyAsync(song, E->aug.song, sizeof(int) * N, hipMemcpyDeviceToDevice, s));
+  if (factor) HIPCHK(hipMemcpyAsync(factor, E->aug.factor, sizeof(double) * N, hipMemcpyDeviceToDevice, s));
+  if (shift) HIPCHK(hipMemcpyAsync(shift, E->aug.shift, sizeof(int) * N, hipMemcpyDeviceToDevice, s));
+  if (T) HIPCHK(hipMemcpyAsync(T, E->aug.T, sizeof(int) * N, hipMemcpyDeviceToDevice, s));
+  if (fallbacks) HIPCHK(hipMemcpyAsync(fallbacks, E->aug.fallbacks, sizeof(int) * N, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+int ps_set_augmentation(ps_env* E, const int32_t* song, const double* factor, const int32_t* shift, void* stream) {
+  if (!E || !song || !factor || !shift) return fail("null argument");
+  GUARD(E);
+  if (!E->aug_on) return fail("the handle has no augmentations (ps_set_augmentations)");
+  return launch_builder(E, AUG_FORCED, nullptr, song, factor, shift, stream);
+}
+
+int ps_get_song_tables(ps_env* E, float* goal, int32_t* count, int32_t* keys, int32_t* fingers, void* stream) {
+  if (!E) return fail("null env");
+  GUARD(E);
+  if (!E->aug_on) return fail("the handle has no augmentations (ps_set_augmentations)");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t rows = (size_t)E->n * E->aug.T_cap;
+  if (goal) HIPCHK(hipMemcpyAsync(goal, E->aug.goal, sizeof(float) * rows * (NK + 1), hipMemcpyDeviceToDevice, s));
+  if (count) HIPCHK(hipMemcpyAsync(count, E->aug.count, sizeof(int) * rows, hipMemcpyDeviceToDevice, s));
+  if (keys) HIPCHK(hipMemcpyAsync(keys, E->aug.keys, sizeof(int) * rows * PS_MAX_NOTES, hipMemcpyDeviceToDevice, s));
+  if (fingers)
+    HIPCHK(hipMemcpyAsync(fingers, E->aug.fingers, sizeof(int) * rows * PS_MAX_NOTES, hipMemcpyDeviceToDevice, s));
   return 0;
 }
 

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/pianosong.h"
+#include "song_build.h"
 
 struct pss_seq {
   std::vector<pss_note> notes;
@@ -439,6 +440,108 @@ int pss_song_tables(const pss_seq* s, double dt, double initial_buffer_time, int
     prev = sus;
     goal[(size_t)t * (NKEYS + 1) + NKEYS] = (float)sus;
   }
+  return 0;
+}
+
+// note_seq.sequences_lib.stretch_note_sequence: every time times the factor; 1.0 is a no-op
+int pss_stretch(pss_seq* s, double factor) {
+  if (!s) return fail("pss_stretch: null sequence");
+  if (!(factor > 0)) return fail("factor must be positive.");  // MidiFile.stretch (midi_file.py:211-212)
+  if (factor == 1.0) return 0;
+  for (auto& n : s->notes) {
+    n.start_time *= factor;
+    n.end_time *= factor;
+  }
+  for (auto& c : s->ccs) c.time *= factor;
+  s->total_time *= factor;
+  return 0;
+}
+
+// note_seq.sequences_lib.transpose_note_sequence(min 21, max 108): notes that leave the piano
+// are removed, and total_time is then the last end of the notes that stay
+int pss_transpose(pss_seq* s, int amount) {
+  if (!s) return fail("pss_transpose: null sequence");
+  if (amount == 0) return 0;
+  std::vector<pss_note> kept;
+  double end = 0.0;
+  for (auto& n : s->notes) {
+    const int p = n.pitch + amount;
+    if (p < MIN_PITCH || p > MAX_PITCH) continue;
+    kept.push_back({p, n.start_time, n.end_time, n.velocity, n.part});
+    end = std::max(end, n.end_time);
+  }
+  if (kept.size() != s->notes.size()) s->total_time = end;
+  s->notes = std::move(kept);
+  return 0;
+}
+
+static_assert(sizeof(pss_flat_song) == sizeof(psb::Song) && sizeof(pss_variation) == sizeof(psb::Var),
+              "pianosong.h mirrors song_build.h");
+
+int pss_flatten(const pss_seq* s, double* notes, double* ccs, int* n_cc64, double* total_time, uint32_t* pitch_mask) {
+  if (!s) return fail("pss_flatten: null sequence");
+  if (s->notes.empty()) return fail("pss_flatten: a song without notes");
+  std::vector<pss_note> sorted = s->notes;
+  std::stable_sort(sorted.begin(), sorted.end(),
+                   [](const pss_note& a, const pss_note& b) { return a.start_time < b.start_time; });
+  uint32_t mask[4] = {0, 0, 0, 0};
+  size_t i = 0;
+  for (auto& n : sorted) {
+    if (n.pitch < MIN_PITCH || n.pitch > MAX_PITCH)
+      return fail("pitch " + std::to_string(n.pitch) + " outside the piano range");
+    if (n.velocity <= 0) return fail("pss_flatten: a note of velocity <= 0");
+    if (n.part < psb::MIN_PART || n.part > psb::MAX_PART) return fail("pss_flatten: note part out of range");
+    if (!(n.start_time >= 0) || !(n.end_time >= 0) || !(n.end_time < 1e9)) return fail("pss_flatten: bad note time");
+    mask[n.pitch >> 5] |= 1u << (n.pitch & 31);
+    if (notes) {
+      notes[4 * i] = n.pitch;
+      notes[4 * i + 1] = n.start_time;
+      notes[4 * i + 2] = n.end_time;
+      notes[4 * i + 3] = n.part;
+    }
+    i++;
+  }
+  int nc = 0;
+  for (auto& c : s->ccs) {
+    if (c.control_number != SUSTAIN_CC) continue;
+    if (!(c.time >= 0)) return fail("pss_flatten: bad control change time");
+    if (ccs) {
+      ccs[2 * nc] = c.time;
+      ccs[2 * nc + 1] = c.control_value;
+    }
+    nc++;
+  }
+  if (n_cc64) *n_cc64 = nc;
+  if (total_time) *total_time = s->total_time;
+  if (pitch_mask) memcpy(pitch_mask, mask, sizeof(mask));
+  return 0;
+}
+
+int pss_build_tables(const pss_flat_song* song, double factor, int shift, double dt, double initial_buffer_time,
+                     int T_cap, float* goal, int32_t* count, int32_t* keys, int32_t* fingers, int* T, int* fell_back) {
+  if (!song || !goal || !count || !keys || !fingers || !T || !fell_back) return fail("pss_build_tables: null argument");
+  if (!(dt > 0)) return fail("pss_build_tables: dt must be positive");
+  if (initial_buffer_time < 0) return fail("initial_buffer_time must be non-negative.");
+  if (!(factor > 0)) return fail("factor must be positive.");
+  const long nbuf = (long)nearbyint(initial_buffer_time / dt);
+  if (T_cap <= nbuf || T_cap > (1 << 24)) return fail("pss_build_tables: T_cap out of range");
+  std::vector<uint32_t> roll((size_t)(T_cap - nbuf) * psb::ROW_WORDS);
+  std::vector<uint8_t> sus((size_t)(T_cap - nbuf));
+  psb::Song s;
+  memcpy(&s, song, sizeof(s));
+  const int rc = psb::build_env(s, factor, shift, 1.0 / dt, nbuf, T_cap, roll.data(), sus.data(), goal, count, keys,
+                                fingers, fell_back, 0, 1);
+  if (rc < 0) return fail("pss_build_tables: the song as given does not fit T_cap rows of at most 16 keys");
+  *T = rc;
+  return 0;
+}
+
+int pss_draw_augmentation(uint64_t seed, uint32_t env, uint32_t episode, const pss_variation* vars, int n_vars,
+                          const pss_flat_song* bank, int n_songs, int* song, double* factor, int* shift) {
+  if (!bank || n_songs < 1 || n_vars < 0 || (n_vars && !vars) || !song || !factor || !shift)
+    return fail("pss_draw_augmentation: bad argument");
+  psb::draw((uint32_t)seed, (uint32_t)(seed >> 32), env, episode, reinterpret_cast<const psb::Var*>(vars), n_vars,
+            reinterpret_cast<const psb::Song*>(bank), n_songs, song, factor, shift);
   return 0;
 }
 

@@ -22,11 +22,11 @@ import enum
 import math
 from dataclasses import dataclass, field
 from pathlib import Path
-from typing import Any, Dict, NamedTuple, Optional, Tuple, Union
+from typing import Any, Dict, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from . import _lib, abi, model as model_lib, music
+from . import _lib, abi, model as model_lib, music, variations
 
 
 # ---------------------------------------------------------------- dm_env (not installed)
@@ -125,6 +125,13 @@ class TaskConfig:
     reduced_action_space: bool = False
     # the forearm slides kept: a subset of ("forearm_tx", "forearm_ty") (shadow_hand.py:270-311)
     forearm_dofs: Tuple[str, ...] = model_lib.FOREARM_DOFS
+    # Per-episode MIDI augmentations (piano_with_shadow_hands.py:62,151-157): variations.MidiSelect /
+    # MidiTemporalStretch / MidiPitchShift / MidiOctaveShift, at most one of each, applied in this
+    # order to the initial song at the start of every episode of every env, on the device.
+    augmentations: Optional[Sequence[Any]] = None
+    # the per-env song tables of an augmented handle may take this many bytes (488 per env and
+    # row: DESIGN.md section 11); more is an error at create
+    augmentation_max_bytes: int = 8 << 30
 
     def lookahead(self) -> int:
         if self.n_seconds_lookahead is not None:
@@ -140,15 +147,19 @@ def _to_sequence(midi) -> music.NoteSequence:
     raise TypeError(f"unsupported midi input {type(midi)!r}")
 
 
+def initial_sequence(midi, cfg: TaskConfig) -> music.NoteSequence:
+    """The task's initial song: the constructor's midi, trimmed when ``trim_silence``
+    (piano_with_shadow_hands.py:100-103)."""
+    seq = _to_sequence(midi)
+    return music.trim_silence(seq) if cfg.trim_silence else seq
+
+
 def compile_task(midi, cfg: TaskConfig, canonical_actions: bool = True):
     """-> (ps_model_desc, SongTables, ps_task_cfg) for a song and task options."""
     if isinstance(midi, music.SongTables):
         song = midi
     else:
-        seq = _to_sequence(midi)
-        if cfg.trim_silence:
-            seq = music.trim_silence(seq)
-        song = music.song_tables(seq, cfg.control_timestep, cfg.initial_buffer_time)
+        song = music.song_tables(initial_sequence(midi, cfg), cfg.control_timestep, cfg.initial_buffer_time)
     hand = None
     if cfg.hand_xml is not None and cfg.primitive_fingertip_collisions is not None:
         raise ValueError("hand_xml and primitive_fingertip_collisions are exclusive: the MJCF names its colliders")
@@ -238,12 +249,43 @@ class BatchedPianoEnv:
             raise _lib.PianosimError("observation / action layout mismatch between the host and the library")
         if env_offset:
             _lib.check(L.ps_set_env_offset(h, int(env_offset)))
+        self.augmentations = None
+        if self.task.augmentations is not None:
+            self._set_augmentations(midi)
         N = self.num_envs
         f32 = dict(device=self.device, dtype=torch.float32)
         self.obs = torch.zeros(N, self.obs_dim, **f32)
         self.reward = torch.zeros(N, **f32)
         self.discount = torch.ones(N, **f32)
         self.step_type = torch.zeros(N, device=self.device, dtype=torch.uint8)
+
+    def _set_augmentations(self, midi) -> None:
+        """TaskConfig.augmentations -> ps_set_augmentations: the bank (the initial song, then
+        MidiSelect's), the variation list and T_cap, the rows the longest song takes at the largest
+        stretch factor."""
+        augs = variations.check(self.task.augmentations)
+        if isinstance(midi, music.SongTables):
+            raise TypeError("augmentations need the song as a NoteSequence or MIDI path, not as SongTables")
+        songs = variations.bank(initial_sequence(midi, self.task), augs)
+        for s in songs[1:]:
+            # fingering_reward and obs_dim are fixed from the constructor's song
+            # (piano_with_shadow_hands.py:110-112)
+            if s.has_fingering() != songs[0].has_fingering():
+                raise ValueError("MidiSelect: every song must agree with the task's song on has_fingering() "
+                                 f"({songs[0].has_fingering()}); {s.title!r} does not")
+        flats = [music.FlatSong.of(s) for s in songs]
+        dt, buf = self.task.control_timestep, self.task.initial_buffer_time
+        fmax = variations.max_stretch(augs)
+        self.T_cap = max(int(f.total_time * fmax * (1.0 / dt) + 1) for f in flats) + int(round(buf / dt))
+        bank = (abi.AugSong * len(flats))()
+        for i, f in enumerate(flats):
+            C.memmove(C.addressof(bank[i]), C.addressof(f), C.sizeof(abi.AugSong))
+        var = (abi.Variation * max(1, len(augs)))(*[abi.Variation(v.kind, v.prob, v.range) for v in augs])
+        desc = abi.AugmentDesc(n_songs=len(flats), songs=bank, n_variations=len(augs), variations=var, dt=dt,
+                               initial_buffer_time=buf, T_cap=self.T_cap,
+                               max_bytes=int(self.task.augmentation_max_bytes))
+        _lib.check(_lib.load().ps_set_augmentations(self._h, C.addressof(desc)))
+        self.augmentations, self.songs = augs, songs
 
     # -- lifecycle
     def close(self):
@@ -392,6 +434,53 @@ class BatchedPianoEnv:
         t = self._torch.as_tensor(dy, device=self.device, dtype=self._torch.float32).contiguous()
         _lib.check(_lib.load().ps_set_hand_offset(self._h, t.data_ptr(), self.stream))
         self._dy = t
+
+    def _augmented(self) -> None:
+        if self.augmentations is None:
+            raise _lib.PianosimError("the env has no augmentations (TaskConfig(augmentations=[...]))")
+
+    def augmentation(self) -> Dict[str, Any]:
+        """This episode's draw of each env (ps_get_augmentation): ``song`` [N] i32 (index into
+        ``self.songs``), ``factor`` [N] f64, ``shift`` [N] i32, the episode's length ``T`` [N] i32
+        and ``fallbacks`` [N] i32 (draws that did not fit and played the selected song as given)."""
+        self._augmented()
+        torch = self._torch
+        i = dict(device=self.device, dtype=torch.int32)
+        out = dict(song=torch.empty(self.num_envs, **i), factor=torch.empty(self.num_envs, device=self.device,
+                                                                            dtype=torch.float64),
+                   shift=torch.empty(self.num_envs, **i), T=torch.empty(self.num_envs, **i),
+                   fallbacks=torch.empty(self.num_envs, **i))
+        _lib.check(_lib.load().ps_get_augmentation(self._h, *(out[k].data_ptr() for k in
+                                                             ("song", "factor", "shift", "T", "fallbacks")),
+                                                   self.stream))
+        return out
+
+    def set_augmentation(self, song, factor, shift) -> None:
+        """Forces every env's draw ([N] each) and rebuilds its tables now; it holds until the
+        env's next reset (ps_set_augmentation)."""
+        self._augmented()
+        torch = self._torch
+        keep = (torch.as_tensor(song, device=self.device).to(torch.int32).contiguous(),
+                torch.as_tensor(factor, device=self.device).to(torch.float64).contiguous(),
+                torch.as_tensor(shift, device=self.device).to(torch.int32).contiguous())
+        for t in keep:
+            if t.shape != (self.num_envs,):
+                raise ValueError(f"set_augmentation takes [{self.num_envs}] arrays, got {tuple(t.shape)}")
+        _lib.check(_lib.load().ps_set_augmentation(self._h, *(t.data_ptr() for t in keep), self.stream))
+        self._forced = keep
+
+    def song_tables(self) -> Dict[str, Any]:
+        """Each env's own tables (ps_get_song_tables): ``goal`` [N, T_cap, 89] f32, ``count``
+        [N, T_cap], ``keys`` / ``fingers`` [N, T_cap, 16] i32; rows >= T of an env are stale."""
+        self._augmented()
+        torch = self._torch
+        N, Tc = self.num_envs, self.T_cap
+        i = dict(device=self.device, dtype=torch.int32)
+        out = dict(goal=torch.empty(N, Tc, abi.NKEY + 1, device=self.device), count=torch.empty(N, Tc, **i),
+                   keys=torch.empty(N, Tc, abi.MAX_NOTES, **i), fingers=torch.empty(N, Tc, abi.MAX_NOTES, **i))
+        _lib.check(_lib.load().ps_get_song_tables(self._h, *(out[k].data_ptr() for k in
+                                                            ("goal", "count", "keys", "fingers")), self.stream))
+        return out
 
     def obs_dict(self, obs=None) -> Dict[str, Any]:
         obs = self.obs if obs is None else obs
@@ -550,7 +639,10 @@ def song_for(environment_name: str, midi_file=None) -> music.NoteSequence:
     return _DEBUG_SONGS[environment_name]()
 
 
-def load(environment_name: str, midi_file=None, seed=None, task_kwargs=None, device=None) -> Environment:
-    """``robopianist.suite.load`` (suite/__init__.py:50-93) for the debug songs / MIDI files."""
-    return Environment(song_for(environment_name, midi_file), TaskConfig(**(task_kwargs or {})), device=device,
-                       seed=0 if seed is None else int(seed))
+def load(environment_name: str, midi_file=None, seed=None, stretch: float = 1.0, shift: int = 0, task_kwargs=None,
+         device=None) -> Environment:
+    """``robopianist.suite.load`` (suite/__init__.py:50-93) for the debug songs / MIDI files;
+    ``stretch`` then ``shift`` are applied to the song as ``music.load`` does
+    (music/__init__.py:92)."""
+    song = music.transpose(music.stretch(song_for(environment_name, midi_file), stretch), shift)
+    return Environment(song, TaskConfig(**(task_kwargs or {})), device=device, seed=0 if seed is None else int(seed))

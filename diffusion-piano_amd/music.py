@@ -162,6 +162,73 @@ def trim_silence(seq: NoteSequence) -> NoteSequence:
     return s.sequence(seq.title)
 
 
+def stretch(seq: NoteSequence, factor: float) -> NoteSequence:
+    """``MidiFile.stretch`` (midi_file.py:204-214) over ``stretch_note_sequence``
+    (``pss_stretch``): every note and control-change time and ``total_time`` times ``factor``;
+    1.0 is a no-op, a factor <= 0 raises."""
+    s = _Seq.of(seq)
+    _check(_lib.load_song().pss_stretch(s.h, float(factor)))
+    return s.sequence(seq.title)
+
+
+def transpose(seq: NoteSequence, amount: int) -> NoteSequence:
+    """``MidiFile.transpose`` (midi_file.py:216-229) over ``transpose_note_sequence``
+    (``pss_transpose``): notes that leave MIDI 21..108 are removed; 0 is a no-op."""
+    s = _Seq.of(seq)
+    _check(_lib.load_song().pss_transpose(s.h, int(amount)))
+    return s.sequence(seq.title)
+
+
+class FlatSong(C.Structure):
+    """``pss_flat_song``: a song as the per-episode builder reads it (``pss_flatten``)."""
+    _fields_ = [("notes", C.c_void_p), ("ccs", C.c_void_p), ("n_notes", C.c_int32), ("n_cc", C.c_int32),
+                ("total_time", C.c_double), ("pitch_mask", C.c_uint32 * 4)]
+
+    @classmethod
+    def of(cls, seq: NoteSequence) -> "FlatSong":
+        L = _lib.load_song()
+        s = _Seq.of(seq)
+        ncc, tt = C.c_int(), C.c_double()
+        mask = (C.c_uint32 * 4)()
+        _check(L.pss_flatten(s.h, None, None, C.byref(ncc), C.byref(tt), mask))
+        notes = np.zeros((len(seq.notes), 4), np.float64)
+        ccs = np.zeros((max(1, ncc.value), 2), np.float64)
+        _check(L.pss_flatten(s.h, notes.ctypes.data, ccs.ctypes.data, None, None, None))
+        out = cls(notes.ctypes.data, ccs.ctypes.data, len(seq.notes), ncc.value, tt.value, mask)
+        out._arrays = (notes, ccs)  # kept alive with the struct
+        return out
+
+    def pitches(self) -> List[int]:
+        return [p for p in range(128) if (self.pitch_mask[p >> 5] >> (p & 31)) & 1]
+
+
+class Variation(C.Structure):
+    """``pss_variation`` (kind 1 select, 2 stretch, 3 pitch shift, 4 octave shift)."""
+    _fields_ = [("kind", C.c_int32), ("prob", C.c_double), ("range", C.c_double)]
+
+
+def build_tables(song, factor: float, shift: int, dt: float, initial_buffer_time: float = 0.0,
+                 T_cap: Optional[int] = None, name: str = ""):
+    """The device builder's code on the host (``pss_build_tables``): ``(SongTables, fell_back)``
+    of ``song`` (a NoteSequence or FlatSong) stretched by ``factor`` and transposed by ``shift``.
+    ``T_cap``: rows the tables may take (default: as many as this draw needs)."""
+    flat = song if isinstance(song, FlatSong) else FlatSong.of(song)
+    if T_cap is None:
+        T_cap = int(flat.total_time * max(float(factor), 1.0) / dt) + int(round(initial_buffer_time / dt)) + 3
+    goal = np.zeros((T_cap, NUM_KEYS + 1), np.float32)
+    count = np.zeros(T_cap, np.int32)
+    keys = np.full((T_cap, MAX_NOTES_PER_STEP), -1, np.int32)
+    fingers = np.full((T_cap, MAX_NOTES_PER_STEP), -1, np.int32)
+    T, fb = C.c_int(), C.c_int()
+    _check(_lib.load_song().pss_build_tables(C.addressof(flat), float(factor), int(shift), float(dt),
+                                             float(initial_buffer_time), int(T_cap), goal.ctypes.data,
+                                             count.ctypes.data, keys.ctypes.data, fingers.ctypes.data,
+                                             C.byref(T), C.byref(fb)))
+    n = T.value
+    has_f = len({int(x) for x in flat._arrays[0][:, 3]}) > 1 and bool((flat._arrays[0][:, 3] != 0).any())
+    return SongTables(name, goal[:n], count[:n], keys[:n], fingers[:n], has_f), bool(fb.value)
+
+
 _NOTE_VALUES = {
     "C": 0, "C#": 1, "Db": 1, "D": 2, "D#": 3, "Eb": 3, "E": 4, "F": 5, "F#": 6,
     "Gb": 6, "G": 7, "G#": 8, "Ab": 8, "A": 9, "A#": 10, "Bb": 10, "B": 11,

@@ -380,6 +380,72 @@ int ps_set_hand_offset(ps_env* env, const float* dy, void* stream);
  * ("Philox streams are keyed by global env id"). */
 int ps_set_env_offset(ps_env* env, int64_t global_first_env);
 
+/* ---- per-episode MIDI augmentations (PianoWithShadowHands(augmentations=...),
+ * piano_with_shadow_hands.py:62,151-157,169-174, over the Variations of suite/variations.py:
+ * MidiSelect, MidiTemporalStretch, MidiPitchShift, MidiOctaveShift). Every episode of every env,
+ * the first reset included, starts again from the bank's song 0 (the song given to ps_create),
+ * applies the variations in list order and plays the result. Which envs start an episode is
+ * known on the device only (auto-reset after LAST), so the draw and the env's new song tables
+ * are made there, by a builder kernel that ps_reset and ps_step enqueue before their own: no
+ * host sync, legal under stream capture. The draw is counter-based (Philox4x32-10 keyed by the
+ * handle's seed, counter (episode, global env id, "midi", index in the list)), not numpy's
+ * RandomState stream; DESIGN.md states it and variations.draw restates it in Python.
+ *
+ * A song of the bank (host memory; copied): notes (pitch, start, end, part) as fp64, stably
+ * sorted by start time, the CC64 events (time, value) in sequence order, total_time, one bit per
+ * MIDI pitch that occurs (word p / 32, bit p % 32). Layout of pss_flat_song (pianosong.h),
+ * whose pss_flatten writes it. A positive stretch factor keeps the order: the device never sorts. */
+typedef struct {
+  const double* notes;
+  const double* ccs;
+  int32_t n_notes, n_cc;
+  double total_time;
+  uint32_t pitch_mask[4];
+} ps_aug_song;
+#define PS_VAR_SELECT 1   /* one of songs 1 .. n_songs - 1, uniformly; no gate */
+#define PS_VAR_STRETCH 2  /* factor uniform on [1 - range, 1 + range] */
+#define PS_VAR_PITCH 3    /* semitones uniform on [max(21 - min_pitch, -range), min(108 - max_pitch, range)] */
+#define PS_VAR_OCTAVE 4   /* 12 x uniform on [low // 12, high // 12] of the bounds at 12 * range */
+#define PS_MAX_VARIATIONS 4
+typedef struct {
+  int32_t kind;
+  double prob;  /* the variation is skipped when u > prob */
+  double range; /* 0: no-op */
+} ps_variation;
+typedef struct {
+  uint32_t struct_size;  /* sizeof(ps_augment_desc), as ps_task_cfg.struct_size */
+  int32_t n_songs;
+  const ps_aug_song* songs;
+  int32_t n_variations;  /* <= PS_MAX_VARIATIONS */
+  const ps_variation* variations;
+  double dt, initial_buffer_time;  /* the control timestep and buffer the song of ps_create was built with */
+  int32_t T_cap;       /* rows of one env's tables: the most frames any song takes at the largest
+                          stretch factor, plus the buffer frames */
+  uint64_t max_bytes;  /* budget of the per-env tables (n_envs * T_cap * 488 B); 0: none */
+} ps_augment_desc;
+#define PS_AUGMENT_DESC_SIZE ((uint32_t)sizeof(ps_augment_desc))
+/* Init-time (it allocates and synchronises): call before the first reset. NULL turns the
+ * augmentations off and frees the bank. Every env starts with the tables of song 0 as given.
+ * Fails, with the sizes in the message, when the per-env tables exceed max_bytes, when a song
+ * as given does not fit T_cap rows of at most PS_MAX_NOTES keys, or when the builder's roll
+ * ((T_cap - buffer frames) * 89 B) does not fit the 64 KB of LDS a workgroup may take. */
+int ps_set_augmentations(ps_env* env, const ps_augment_desc* desc);
+/* This episode's draw of each env: song [N] i32 (index into the bank), factor [N] f64, shift [N]
+ * i32 (semitones), its length T [N] i32, and fallbacks [N] i32: how often since
+ * ps_set_augmentations a draw would have needed more than T_cap rows or put more than
+ * PS_MAX_NOTES keys into one row - that episode then plays the selected song at factor 1.0 and
+ * shift 0 (a truncated table is never written). Device pointers; any may be NULL. */
+int ps_get_augmentation(ps_env* env, int32_t* song, double* factor, int32_t* shift, int32_t* T,
+                        int32_t* fallbacks, void* stream);
+/* Forces the draw of every env (device arrays [N]) and rebuilds its tables now; it holds until
+ * the env's next reset, like ps_set_hand_offset (teacher-forced parity). */
+int ps_set_augmentation(ps_env* env, const int32_t* song, const double* factor, const int32_t* shift,
+                        void* stream);
+/* The per-env tables: goal [N][T_cap][89] f32, count [N][T_cap], keys / fingers
+ * [N][T_cap][PS_MAX_NOTES] i32 (device; any may be NULL); rows >= T of an env are stale. */
+int ps_get_song_tables(ps_env* env, float* goal, int32_t* count, int32_t* keys, int32_t* fingers,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

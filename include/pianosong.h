@@ -68,6 +68,49 @@ int pss_trim_silence(pss_seq* seq);
 int pss_song_tables(const pss_seq* seq, double dt, double initial_buffer_time, int max_T, int max_notes,
                     float* goal, int32_t* count, int32_t* keys, int32_t* fingers, int* T);
 
+/* MidiFile.stretch / MidiFile.transpose (midi_file.py:204-229), in place. note_seq is absent
+ * here; the semantics of the two sequences_lib calls underneath are restated from upstream
+ * knowledge, as pretty_midi's are above:
+ *   stretch_note_sequence: every note start and end, every control-change time and total_time
+ *     are multiplied by the factor (fp64); factor 1.0 is a no-op; factor <= 0 is an error.
+ *   transpose_note_sequence(min 21, max 108): pitch += amount; a note that leaves the piano is
+ *     removed, and when one was removed total_time becomes the last end of the notes that stay;
+ *     amount 0 is a no-op. */
+int pss_stretch(pss_seq* seq, double factor);
+int pss_transpose(pss_seq* seq, int amount);
+
+/* The per-episode MIDI augmentations (suite/variations.py; ps_set_augmentations of pianosim.h).
+ * A song in the form the device builder reads: notes (pitch, start, end, part) as fp64, stably
+ * sorted by start time; the CC64 events (time, value) in sequence order; total_time; a bit per
+ * MIDI pitch that occurs (word p / 32, bit p % 32). pss_flatten writes it (notes [n_notes][4],
+ * ccs [n_cc64][2]; either may be NULL to get the sizes) and refuses a song the builder cannot
+ * take: no notes, a pitch off the piano, a velocity <= 0, a negative time, a part outside -1..61. */
+typedef struct {
+  const double* notes;
+  const double* ccs;
+  int32_t n_notes, n_cc;
+  double total_time;
+  uint32_t pitch_mask[4];
+} pss_flat_song;
+typedef struct {
+  int32_t kind; /* 1 MidiSelect, 2 MidiTemporalStretch, 3 MidiPitchShift, 4 MidiOctaveShift */
+  double prob, range;
+} pss_variation;
+int pss_flatten(const pss_seq* seq, double* notes, double* ccs, int* n_cc64, double* total_time,
+                uint32_t* pitch_mask);
+/* The device builder's own code (csrc/song_build.h) on the host: the tables of `song` stretched
+ * by factor and transposed by shift, equal to pss_song_tables(pss_transpose(pss_stretch(seq)))
+ * with max_notes 16. goal [T_cap][89], count [T_cap], keys / fingers [T_cap][16]; rows >= *T are
+ * left alone. When the result would have more than T_cap rows or more than 16 keys in a row,
+ * the tables are those of the song as given and *fell_back is 1. */
+int pss_build_tables(const pss_flat_song* song, double factor, int shift, double dt, double initial_buffer_time,
+                     int T_cap, float* goal, int32_t* count, int32_t* keys, int32_t* fingers, int* T,
+                     int* fell_back);
+/* The builder's draw of (seed, global env, episode) over a bank whose song 0 is the task's own
+ * (variations.draw in Python is its specification). */
+int pss_draw_augmentation(uint64_t seed, uint32_t env, uint32_t episode, const pss_variation* vars, int n_vars,
+                          const pss_flat_song* bank, int n_songs, int* song, double* factor, int* shift);
+
 #ifdef __cplusplus
 }
 #endif
