@@ -1991,20 +1991,47 @@ enum : int { QC_HEAD = 0, QC_TAIL = 32, QC_WORDS = 64 };  // (the two counters o
 // handed over inside a launch: the env's other rows are read by its first chunk and written by
 // its last.
 enum : int { QE_NONE = -1, QE_LEFT = -2 };
+// The queue kernel's one parameter: it sits at offset 0 of the kernel-argument segment, and the
+// item loop reads it there (below).
+struct QArgs {
+  const DevModel* m;
+  Song song;
+  Cfg cfg;
+  Bufs bufs;
+  const float* action;
+  float *obs, *reward, *discount;
+  uint8_t* step_type;
+  int n_envs;
+  int *queue, *ctr;
+  int cap, chunks;
+};
+// Nothing is item-invariant in the loop: every trip reads what it uses - and what env_step
+// receives - through a pointer to the kernel-argument segment that an empty asm makes opaque,
+// and takes its lane id through another. With `a` = the parameter itself the compiler hoists
+// the address arithmetic and lane constants derived from the arguments and the lane id out of
+// the loop, has no registers for them across the step body, and spills them: +592 B of scratch
+// per lane in both instantiations, ~160 more VGPR spills (measured; DESIGN.md section 5). Through
+// the opaque pointer the arguments are scalar loads (constant address space, the pointer is
+// uniform) where the body first uses them, and only the pointer itself is live across the back
+// edge: 219 fewer SGPR spills than with the arguments held from the prologue.
 template <bool XG>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PS_WAVES_PER_EU))) pianosim_queue_kernel(
-    const DevModel* __restrict__ m, Song song, Cfg cfg, Bufs bufs, const float* __restrict__ action,
-    float* __restrict__ obs, float* __restrict__ reward, float* __restrict__ discount, uint8_t* __restrict__ step_type,
-    int n_envs, int* queue, int* ctr, int cap, int chunks) {
+    const QArgs ka) {
   __shared__ Shared S;
-  const int lane = threadIdx.x;
+  typedef __attribute__((address_space(4))) const QArgs* KArgs;
+  const uint64_t kbase = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr();
   // the first item: queue[blockIdx.x] (grid <= n_envs; written by order_kernel)
-  int own = queue[blockIdx.x];  // an item this workgroup already holds, or QE_NONE: pop one
+  int own = ka.queue[blockIdx.x];  // an item this workgroup already holds, or QE_NONE: pop one
   for (;;) {
+    int lane = threadIdx.x;
+    asm volatile("" : "+v"(lane));
+    uint64_t kp = kbase;
+    asm volatile("" : "+s"(kp));
+    const QArgs& a = *(const QArgs*)(KArgs)kp;
     int item = own;
     if (own < 0 && lane == 0) {
-      const int t = __hip_atomic_fetch_add(&ctr[QC_HEAD], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (t < cap) item = __hip_atomic_exchange(&queue[t], QE_LEFT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int t = __hip_atomic_fetch_add(&a.ctr[QC_HEAD], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (t < a.cap) item = __hip_atomic_exchange(&a.queue[t], QE_LEFT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the acquire's invalidate has completed)
@@ -2014,9 +2041,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PS_WAVE
     wsync();
     if (item < 0) return;
     const int e = item >> 4, chunk = item & 15;
-    if (e >= n_envs) return;  // (never: order_kernel and the continuations write valid items only)
-    const bool more = env_step<XG, PS_WAVES_PER_EU, true>(S, m, song, cfg, bufs, action, nullptr, obs, reward, discount,
-                                                          step_type, 0, e, lane, chunk, chunks);
+    if (e >= a.n_envs) return;  // (never: order_kernel and the continuations write valid items only)
+    const bool more = env_step<XG, PS_WAVES_PER_EU, true>(S, a.m, a.song, a.cfg, a.bufs, a.action, nullptr, a.obs, a.reward,
+                                                          a.discount, a.step_type, 0, e, lane, chunk, a.chunks);
     // (uniform: the whole wave returns the same) every lane's write-through stores have completed
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     wsync();
@@ -2025,10 +2052,10 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PS_WAVE
       const int next = (e << 4) | (chunk + 1);
       int old = QE_NONE;
       if (lane == 0) {
-        const int slot = __hip_atomic_fetch_add(&ctr[QC_TAIL], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int slot = __hip_atomic_fetch_add(&a.ctr[QC_TAIL], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // (slot < cap always: at most `chunks` items per env; past it the item stays here)
-        old = slot < cap ? __hip_atomic_exchange(&queue[slot], next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                         : (int)QE_LEFT;
+        old = slot < a.cap ? __hip_atomic_exchange(&a.queue[slot], next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                           : (int)QE_LEFT;
       }
       if (__builtin_amdgcn_readfirstlane(old) == QE_LEFT) own = next;
     }

@@ -782,9 +782,10 @@ static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask,
                        E->n, E->queue, E->qctr, cap, grid, E->ordered);
     HIPCHK(hipGetLastError());
 #ifndef PS_TIMING
+    const QArgs qa{E->d_model, song, cfg, b, action, obs, reward, discount, step_type, E->n, E->queue, E->qctr, cap,
+                   E->chunks};
 #define PS_LAUNCH_Q(XG)                                                                                           \
-  hipLaunchKernelGGL((pianosim_queue_kernel<XG>), dim3(grid), dim3(64), 0, (hipStream_t)stream, E->d_model, song, \
-                     cfg, b, action, obs, reward, discount, step_type, E->n, E->queue, E->qctr, cap, E->chunks)
+  hipLaunchKernelGGL((pianosim_queue_kernel<XG>), dim3(grid), dim3(64), 0, (hipStream_t)stream, qa)
     if (E->has_x) PS_LAUNCH_Q(true); else PS_LAUNCH_Q(false);
 #undef PS_LAUNCH_Q
 #endif

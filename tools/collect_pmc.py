@@ -1,4 +1,5 @@
-"""Summarise rocprofv3 outputs for pianosim_kernel into profiles/.
+"""Summarise rocprofv3 outputs for the step kernel into profiles/: pianosim_queue_kernel (the
+time-sliced step, launches of more than 2048 envs) where the run has it, else pianosim_kernel.
 
 usage: python tools/collect_pmc.py <trace_dir> <fetch_dir> <write_dir> <envs> <song> <out_prefix> [warmup] [sq_dir]
 
@@ -29,7 +30,8 @@ def rows(d, pattern):
 # its kernel instantiation: pianosim_kernel<true> (box / hull colliders) or <false> (all-capsule
 # hand); bench.py's line also times the other sets (its legs), which must not mix in
 HAND = __import__("os").environ.get("PIANOSIM_HAND", "hull")
-KNAME = "pianosim_kernel<false" if HAND == "authored" else "pianosim_kernel<true"  # <XG, waves per SIMD>
+XG = "<false" if HAND == "authored" else "<true"  # <XG, waves per SIMD> / <XG>
+KNAME = "pianosim_kernel" + XG  # (main() switches to the queue kernel when the trace has it)
 
 
 def counter(d, name):
@@ -52,6 +54,11 @@ def main():
     tdir, fdir, wdir, envs, song, prefix = sys.argv[1:4] + [int(sys.argv[4])] + sys.argv[5:7]
     warmup = int(sys.argv[7]) if len(sys.argv) > 7 else 5
     sqdir = sys.argv[8] if len(sys.argv) > 8 else None
+    global KNAME
+    if any("pianosim_queue_kernel" + XG in r.get("Kernel_Name", "") for r in rows(tdir, "*kernel_trace.csv")):
+        KNAME, resets = "pianosim_queue_kernel" + XG, 0  # (the reset is a pianosim_kernel launch)
+    else:
+        resets = 1
     stats = [r for r in rows(tdir, "*kernel_stats.csv") if KNAME in r.get("Name", "")]
     fetch_kb = counter(fdir, "FETCH_SIZE")
     write_kb = counter(wdir, "WRITE_SIZE")
@@ -66,7 +73,7 @@ def main():
     # the timed steps only: bench.py launches reset (1) + warmup (5) before the timed region
     tr = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows(tdir, "*kernel_trace.csv")
                 if KNAME in r.get("Kernel_Name", ""))
-    timed = [e - b for b, e in tr[1 + warmup:]]
+    timed = [e - b for b, e in tr[resets + warmup:]]
     if timed:
         out["rocprof_avg_ns"] = sum(timed) / len(timed)
         out["rocprof_timed_launches"] = len(timed)

@@ -1,9 +1,34 @@
-# Development aid: register / scratch / LDS use of the step kernel's instantiations, from the
-# compiler's resource-usage remarks on a device-only compile with the product flags
+# Development aid: register / scratch / LDS use and spill counts of the step kernels'
+# instantiations (pianosim_kernel<XG, WPE>, and pianosim_queue_kernel<XG>, the time-sliced step
+# that launches of more than 2048 envs - the benchmark's - run), and the frames of the
+# out-of-line narrow phases they call (x_pairs, x_refine: part of the caller's scratch), from the
+# code object metadata and symbols of a device-only compile to assembly with the product flags
 # (__graft_entry__._hipcc_lib). usage: bash tools/resource_usage.sh [extra hipcc flags]
 cd "$(dirname "$0")/.."
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -Wno-unused-value --cuda-device-only -c \
+S=$(mktemp /tmp/ps_dev.XXXXXX.s)
+trap 'rm -f "$S"' EXIT
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -Wno-unused-value --cuda-device-only -S \
   -fno-hip-fp32-correctly-rounded-divide-sqrt -falign-loops=64 -mllvm -amdgpu-sched-strategy=max-ilp \
-  -Rpass-analysis=kernel-resource-usage "$@" -o /tmp/ps_dev.o diffusion-piano_amd/csrc/pianosim.hip 2>&1 |
-  grep -E "Function Name|VGPRs:|AGPRs:|ScratchSize|Occupancy|LDS Size" | sed 's/.*remark: //' |
-  paste - - - - - - | grep pianosim_kernel
+  "$@" -o "$S" diffusion-piano_amd/csrc/pianosim.hip || exit 1
+awk '
+  # out-of-line device functions: .set .L<symbol>.<field>, <value>
+  /^[ \t]*\.set \.L_Z[0-9]+x_(pairs|refine)/ {
+    split($2, a, "."); sym = a[2]; sub(/^L/, "", sym); f = a[3]; sub(/,$/, "", f)
+    if (f == "num_vgpr") fv[sym] = $3
+    if (f == "private_seg_size") { fs[sym] = $3; forder[++nf] = sym }
+  }
+  # kernels: one amdhsa.kernels metadata entry each (its keys are sorted, .agpr_count first)
+  /^  - \.agpr_count:/ { if (name != "") emit(); name = "-"; delete k }
+  name != "" && /^    \.[a-z_]+:/ { key = $1; sub(/^\./, "", key); sub(/:$/, "", key); k[key] = $2; if (key == "name") name = $2 }
+  /^  - \.agpr_count:/ { k["agpr_count"] = $3 }
+  /^amdhsa\.target:/ { if (name != "") emit(); name = "" }
+  function emit() {
+    if (name !~ /pianosim_(queue_)?kernel/) return
+    printf "%s\tVGPRs: %s\tAGPRs: %s\tSGPRs: %s\tScratchSize [bytes/lane]: %s\tVGPR spills: %s\tSGPR spills: %s\tLDS Size [bytes/block]: %s\n",
+      name, k["vgpr_count"] - k["agpr_count"], k["agpr_count"], k["sgpr_count"], k["private_segment_fixed_size"],
+      k["vgpr_spill_count"], k["sgpr_spill_count"], k["group_segment_fixed_size"]
+  }
+  END {
+    for (i = 1; i <= nf; i++)
+      printf "%s\t(out of line) VGPRs: %s\tframe [bytes/lane]: %s\n", forder[i], fv[forder[i]], fs[forder[i]]
+  }' "$S"
