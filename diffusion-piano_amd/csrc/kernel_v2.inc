@@ -1330,14 +1330,16 @@ __device__ __forceinline__ void key_state2(const DevModel* __restrict__ m, Share
 #define PS_WAVES_PER_EU 2
 #endif
 #ifndef PS_CHUNKS
-#define PS_CHUNKS 3  // chunks of substeps per env-step on the time-sliced path (pianosim_queue_kernel)
+#define PS_CHUNKS 6  // chunks of substeps per env-step on the time-sliced path (pianosim_queue_kernel):
+                     // 10 substeps as 2 2 2 2 1 1; measured 3 to 10, profiles/r09_v1_bench_ab.txt
 #endif
 // WPE: resident waves per SIMD the register allocation is built for. 2 (the default): 256 VGPRs,
 // the solve's overflow spilled to scratch; 1: 256 VGPRs + AGPRs, no scratch - chosen by the host
 // when the launch is at most one wave per SIMD anyway (launch() below)
 //
 // env_step: the control step of env e by one wave, or (Q, the queue path) its chunk `chunk` of
-// `chunks`: substeps [chunk * nsub / chunks, (chunk + 1) * nsub / chunks). A chunk that is not
+// `chunks`: nsub / chunks substeps, one more in the first nsub % chunks chunks (the env's last
+// chunk, which also runs the task layer, is never the one with more). A chunk that is not
 // the env's last leaves the state live across the substep boundary in the env's park row (CW_*)
 // and returns true: the caller publishes the continuation; the last chunk also runs the task
 // layer and writes the outputs. Every chunk sets up what it uses (LDS words, lane constants,
@@ -1482,8 +1484,10 @@ __device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__
       guess.valid = __builtin_amdgcn_readlane(cscal, CS_GVALID) != 0;
     }
     // (acc_reset is false at every substep boundary: a substep that completes clears it)
-    const int s_begin = Q ? chunk * m->nsub / chunks : 0;
-    const int s_end = Q ? (chunk + 1) * m->nsub / chunks : m->nsub;
+    // (the substeps that do not divide evenly go to the first chunks: 10 in 3 = [0,4) [4,7) [7,10))
+    const int s_each = Q ? m->nsub / chunks : 0, s_more = Q ? m->nsub - s_each * chunks : 0;
+    const int s_begin = Q ? chunk * s_each + min(chunk, s_more) : 0;
+    const int s_end = Q ? (chunk + 1) * s_each + min(chunk + 1, s_more) : m->nsub;
     for (int s = s_begin; s < (Q ? s_end : m->nsub); s++) {
       {  // mj_checkPos, mj_checkVel (mju_isBad: NaN or |x| > 1e10)
         bool bq = lane < NDT && !(fabsf(D.q) <= 1e10f), bv = false;
@@ -1959,24 +1963,31 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
   env_step<XG, WPE, false>(S, m, song, cfg, bufs, action, mask, obs, reward, discount, step_type, mode, e, lane, 0, 1);
 }
 
-enum : int { QC_HEAD = 0, QC_TAIL = 32, QC_WORDS = 64 };  // (the two counters on lines of their own)
+enum : int { QC_HEAD = 0, QC_WORDS = 32 };  // (the ticket counter on a line of its own)
 #ifndef PS_TIMING  // (the timing build's per-env accumulators are those of whole steps)
 // The step of a launch of more envs than resident wave slots, time-sliced: the grid is the
-// resident slots, and every workgroup takes (env, chunk) items off a FIFO in global memory
-// until it finds none. order_kernel has put the n chunk-0 items at the front (queue[0..n),
-// longest expected first), set queue[n..cap) to QE_NONE (unpublished) and ctr[QC_HEAD] = the
-// grid (workgroup b starts with item b), ctr[QC_TAIL] = n. A workgroup that finishes a chunk
-// with substeps left reserves the slot ctr[QC_TAIL]++ and publishes the env's next chunk there;
-// each env has at most `chunks` items, so cap = n * chunks slots always suffice.
+// resident slots, and every workgroup takes (env, chunk) items off a queue in global memory
+// until the tickets run out. Every item's slot is known in advance: (chunk c, rank r) lives at
+// queue[c * n + r], r = rank[env] the env's position in order_kernel's order of this step
+// (longest expected first). order_kernel has written the n chunk-0 items (queue[0..n)), set
+// queue[n..cap) to QE_NONE (unpublished) and ctr[QC_HEAD] = the grid (workgroup b starts with
+// item b). Tickets t = ctr[QC_HEAD]++ walk the slots in that order - round 0 by rank, round 1
+// by rank, ... - so in every round the envs expected longest are picked up first and the items
+// that end the launch are the short ones. (With tail append - every continuation at
+// ctr[tail]++ - the queue was in completion order from round 1 on: every env's next chunk
+// waited behind a whole batch, the expensive envs' as long as any, and the launch ended 1 ms
+// after the first workgroup found the queue empty, on the longest last chunks;
+// profiles/r09_v1_queue_trace_parent.txt.)
 //
-// No workgroup ever waits for another, and no step of the protocol is retried. A pop takes the
-// ticket t = ctr[QC_HEAD]++ and EXCHANGES queue[t] with QE_LEFT: it gets the item, or (QE_NONE:
-// the queue is empty, t is unpublished or never will be; t >= cap likewise) the workgroup
-// EXITS. A publisher exchanges its item into its slot: if it gets QE_LEFT back, the ticket's
-// holder has left and nobody else will ever read the slot, so the publisher runs the item
-// itself. The exchange decides every slot for exactly one of the two sides, so no item is
-// orphaned and none runs twice; a workgroup leaves only when everything published so far is
-// taken, and what is published later stays with, or behind, a workgroup that is still running.
+// No workgroup ever waits for another, and every loop is bounded by the ticket count. A pop
+// takes a ticket t and EXCHANGES queue[t] with QE_LEFT: it gets the item, or (QE_NONE: the env
+// is behind its schedule, or has no such chunk - an env due for its auto-reset has one) takes
+// the next ticket; at t >= cap the workgroup EXITS: at most cap + grid tickets are taken in a
+// launch. A publisher exchanges its item into its slot: if it gets QE_LEFT back, the ticket's
+// holder has passed and nobody else will ever read the slot, so the publisher runs the item
+// itself, at once: an env behind its schedule stays on its workgroup and waits for nobody. The
+// exchange decides every slot for exactly one of the two sides, so no item is orphaned and
+// none runs twice, and whoever holds an item is running.
 // (A compare-and-swap pop of the head - read head, read entry, swap - was measured first: under
 // 2048 workgroups it succeeds once per round trip, 2-4 us per item, and the 4096-env step took
 // 22 ms against 5.5 ms.)
@@ -2004,7 +2015,24 @@ struct QArgs {
   int n_envs;
   int *queue, *ctr;
   int cap, chunks;
+  const int* rank;
+#ifdef PS_QTRACE
+  unsigned long long* trace;  // the trace build's records (QT_*), zeroed before every launch
+#endif
 };
+// The trace build (-DPS_QTRACE, libpianosim_qtrace.so, tools/queue_trace.py): lane 0 records, for
+// every item run, QT_ITEM words at trace[(chunk * n + env) * QT_ITEM] - the 100 MHz clock when
+// its workgroup turned to the queue (or to the item it already held), when the chunk began and
+// when it ended (stores drained), and ticket << 32 | workgroup (ticket -1: not popped, the
+// workgroup's first item or a continuation it ran itself) - and for every workgroup, behind the
+// cap items, QT_EXIT words: when it left, and the tickets it took that held no item. The
+// product build has none of this.
+enum : int { QT_ITEM = 4, QT_EXIT = 2 };
+#ifdef PS_QTRACE
+#define QT(...) __VA_ARGS__
+#else
+#define QT(...)
+#endif
 // Nothing is item-invariant in the loop: every trip reads what it uses - and what env_step
 // receives - through a pointer to the kernel-argument segment that an empty asm makes opaque,
 // and takes its lane id through another. With `a` = the parameter itself the compiler hoists
@@ -2029,9 +2057,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PS_WAVE
     asm volatile("" : "+s"(kp));
     const QArgs& a = *(const QArgs*)(KArgs)kp;
     int item = own;
+    QT(const unsigned long long qt_turn = __builtin_amdgcn_s_memrealtime(); int qt_ticket = -1;)
     if (own < 0 && lane == 0) {
-      const int t = __hip_atomic_fetch_add(&a.ctr[QC_HEAD], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (t < a.cap) item = __hip_atomic_exchange(&a.queue[t], QE_LEFT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      for (;;) {  // (every trip takes a ticket: at most cap + grid trips in the whole launch)
+        const int t = __hip_atomic_fetch_add(&a.ctr[QC_HEAD], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        QT(qt_ticket = t;)
+        if (t >= a.cap) break;
+        item = __hip_atomic_exchange(&a.queue[t], QE_LEFT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (item >= 0) break;
+        QT(a.trace[(size_t)a.cap * QT_ITEM + blockIdx.x * QT_EXIT + 1] += 1;)
+      }
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the acquire's invalidate has completed)
@@ -2039,23 +2074,34 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PS_WAVE
     // opaque per item: nothing derived from the env is hoisted across items
     asm volatile("" : "+s"(item));
     wsync();
-    if (item < 0) return;
+    if (item < 0) {
+      QT(if (lane == 0) a.trace[(size_t)a.cap * QT_ITEM + blockIdx.x * QT_EXIT] = __builtin_amdgcn_s_memrealtime();)
+      return;
+    }
     const int e = item >> 4, chunk = item & 15;
     if (e >= a.n_envs) return;  // (never: order_kernel and the continuations write valid items only)
+    QT(if (lane == 0) {
+      unsigned long long* rec = a.trace + ((size_t)chunk * a.n_envs + e) * QT_ITEM;
+      rec[0] = qt_turn;
+      rec[1] = __builtin_amdgcn_s_memrealtime();
+      rec[3] = (unsigned long long)(unsigned)qt_ticket << 32 | blockIdx.x;
+    })
     const bool more = env_step<XG, PS_WAVES_PER_EU, true>(S, a.m, a.song, a.cfg, a.bufs, a.action, nullptr, a.obs, a.reward,
                                                           a.discount, a.step_type, 0, e, lane, chunk, a.chunks);
     // (uniform: the whole wave returns the same) every lane's write-through stores have completed
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     wsync();
+    QT(if (lane == 0) a.trace[((size_t)chunk * a.n_envs + e) * QT_ITEM + 2] = __builtin_amdgcn_s_memrealtime();)
     own = QE_NONE;
     if (more) {
       const int next = (e << 4) | (chunk + 1);
       int old = QE_NONE;
       if (lane == 0) {
-        const int slot = __hip_atomic_fetch_add(&a.ctr[QC_TAIL], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // (slot < cap always: at most `chunks` items per env; past it the item stays here)
-        old = slot < a.cap ? __hip_atomic_exchange(&a.queue[slot], next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                           : (int)QE_LEFT;
+        const int slot = (chunk + 1) * a.n_envs + a.rank[e];
+        // (slot < cap always: chunk + 1 < chunks, rank < n; past it the item stays here)
+        old = (unsigned)slot < (unsigned)a.cap
+                  ? __hip_atomic_exchange(&a.queue[slot], next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                  : (int)QE_LEFT;
       }
       if (__builtin_amdgcn_readfirstlane(old) == QE_LEFT) own = next;
     }

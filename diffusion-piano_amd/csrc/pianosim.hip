@@ -67,7 +67,9 @@ struct ps_env {
   // (resident wave slots, or PIANOSIM_STEP_GRID), whether PIANOSIM_CHUNKS forces it for every n
   int chunks, step_grid;
   bool chunks_forced;
-  int *queue, *qctr;        // [n * chunks] items, [QC_WORDS] head / tail counters
+  int *queue, *qctr;        // [chunks][n] items (round, rank), [QC_WORDS] the ticket counter
+  int* qrank;               // [n] env -> its position in order_kernel's order of this step
+  uint64_t* qtrace;         // -DPS_QTRACE: [n * chunks][QT_ITEM] + [grid][QT_EXIT] (ps_debug_qtrace)
   Contact* con_out;         // [N][MAXCON] contact lists of the last step (ps_record_contacts)
   // per-episode MIDI augmentations (ps_set_augmentations): the device bank and per-env tables,
   // the builder's dynamic LDS bytes; every device allocation of it in aug_mem
@@ -560,6 +562,13 @@ int ps_obs_dim(const ps_task_cfg* cfg) {
   return (cfg->n_steps_lookahead + 1) * (NK + 1) + (cfg->fingering_reward ? 10 : 0) + NK + 1 + NH * ND;
 }
 
+#ifdef PS_QTRACE
+static int qtrace_grid(const ps_env* E) { return E->n < E->step_grid ? E->n : E->step_grid; }
+static size_t qtrace_bytes(const ps_env* E) {
+  return sizeof(uint64_t) * ((size_t)E->n * E->chunks * QT_ITEM + (size_t)qtrace_grid(E) * QT_EXIT);
+}
+#endif
+
 int ps_create(const ps_model_desc* model, const ps_song_desc* song, const ps_task_cfg* cfg, int n_envs, int device,
               uint64_t seed, ps_env** out) {
   if (!model || !song || !cfg || !out) return fail("null argument");
@@ -675,6 +684,10 @@ int ps_create(const ps_model_desc* model, const ps_song_desc* song, const ps_tas
     if (E->chunks) {
       HIPCHK(hipMalloc(&E->queue, sizeof(int) * N * E->chunks));
       HIPCHK(hipMalloc(&E->qctr, sizeof(int) * QC_WORDS));
+      HIPCHK(hipMalloc(&E->qrank, sizeof(int) * N));
+#ifdef PS_QTRACE
+      HIPCHK(hipMalloc(&E->qtrace, qtrace_bytes(E)));
+#endif
     }
   }
   *out = E;
@@ -695,6 +708,8 @@ void ps_destroy(ps_env* E) {
   if (E->con_out) hipFree(E->con_out);
   if (E->queue) hipFree(E->queue);
   if (E->qctr) hipFree(E->qctr);
+  if (E->qrank) hipFree(E->qrank);
+  if (E->qtrace) hipFree(E->qtrace);
   free_aug(E);
   delete E;
 }
@@ -707,9 +722,10 @@ void ps_destroy(ps_env* E) {
 // the launch's tail is shorter. Each env's result is independent of the order.
 // With a queue (the time-sliced step, pianosim_queue_kernel) the order is written as the
 // queue's first n items (env << 4 | chunk 0) instead - in env order when `sorted` is false -
-// the other entries are set to -1 (unpublished) and the counters to head = the step's grid
-// (workgroup b starts with item b), tail = n: launched before every such step, so the queue
-// is reset in stream order (and under graph capture).
+// with every env's position in it (qrank: its slot in each later round of the queue); the
+// other entries are set to -1 (unpublished) and the ticket counter to the step's grid
+// (workgroup b starts with item b): launched before every such step, so the queue is reset
+// in stream order (and under graph capture).
 #ifdef PS_DYN_LDS
 #define PS_LAUNCH_LDS PS_DYN_LDS
 #else
@@ -721,16 +737,16 @@ __global__ void __launch_bounds__(ORDER_THREADS) order_kernel(const int* __restr
                                                               const uint8_t* __restrict__ last,
                                                               int* __restrict__ order, int n, int* __restrict__ queue,
                                                               int* __restrict__ qctr, int qcap, int qhead,
-                                                              bool sorted) {
+                                                              bool sorted, int* __restrict__ qrank) {
   __shared__ int hist[ORDER_BUCKETS], base[ORDER_BUCKETS];
   if (queue) {
     for (int i = n + threadIdx.x; i < qcap; i += blockDim.x) queue[i] = -1;
-    if (threadIdx.x == 0) {
-      qctr[QC_HEAD] = qhead;
-      qctr[QC_TAIL] = n;
-    }
+    if (threadIdx.x == 0) qctr[QC_HEAD] = qhead;
     if (!sorted) {
-      for (int e = threadIdx.x; e < n; e += blockDim.x) queue[e] = e << 4;
+      for (int e = threadIdx.x; e < n; e += blockDim.x) {
+        queue[e] = e << 4;
+        qrank[e] = e;
+      }
       return;
     }
   }
@@ -752,8 +768,12 @@ __global__ void __launch_bounds__(ORDER_THREADS) order_kernel(const int* __restr
   for (int e = threadIdx.x; e < n; e += blockDim.x) {
     const int b = last[e] ? 0 : 1 + min(max(stats[(size_t)e * PS_NSTATS + PS_STAT_SOLVES], 0), 128);
     const int pos = atomicAdd(&base[b], 1);
-    if (queue) queue[pos] = e << 4;
-    else order[pos] = e;
+    if (queue) {
+      queue[pos] = e << 4;
+      qrank[e] = pos;
+    } else {
+      order[pos] = e;
+    }
   }
 }
 
@@ -779,11 +799,17 @@ static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask,
   if (sliced) {
     const int cap = E->n * E->chunks, grid = E->n < E->step_grid ? E->n : E->step_grid;
     hipLaunchKernelGGL(order_kernel, dim3(1), dim3(ORDER_THREADS), 0, (hipStream_t)stream, E->stats, E->last, E->order,
-                       E->n, E->queue, E->qctr, cap, grid, E->ordered);
+                       E->n, E->queue, E->qctr, cap, grid, E->ordered, E->qrank);
     HIPCHK(hipGetLastError());
 #ifndef PS_TIMING
+#ifdef PS_QTRACE
+    HIPCHK(hipMemsetAsync(E->qtrace, 0, qtrace_bytes(E), (hipStream_t)stream));
     const QArgs qa{E->d_model, song, cfg, b, action, obs, reward, discount, step_type, E->n, E->queue, E->qctr, cap,
-                   E->chunks};
+                   E->chunks, E->qrank, (unsigned long long*)E->qtrace};
+#else
+    const QArgs qa{E->d_model, song, cfg, b, action, obs, reward, discount, step_type, E->n, E->queue, E->qctr, cap,
+                   E->chunks, E->qrank};
+#endif
 #define PS_LAUNCH_Q(XG)                                                                                           \
   hipLaunchKernelGGL((pianosim_queue_kernel<XG>), dim3(grid), dim3(64), 0, (hipStream_t)stream, qa)
     if (E->has_x) PS_LAUNCH_Q(true); else PS_LAUNCH_Q(false);
@@ -795,7 +821,7 @@ static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask,
   const int* order = nullptr;
   if (mode == 0 && E->ordered && E->n >= 2048) {  // below one wave of workgroups there is no tail to balance
     hipLaunchKernelGGL(order_kernel, dim3(1), dim3(ORDER_THREADS), 0, (hipStream_t)stream, E->stats, E->last, E->order,
-                       E->n, (int*)nullptr, (int*)nullptr, 0, 0, true);
+                       E->n, (int*)nullptr, (int*)nullptr, 0, 0, true, (int*)nullptr);
     HIPCHK(hipGetLastError());
     order = E->order;
   }
@@ -906,6 +932,24 @@ int ps_debug_timing(ps_env* E, uint64_t* out) {
   HIPCHK(hipDeviceSynchronize());
   if (out) HIPCHK(hipMemcpy(out, d, bytes, hipMemcpyDeviceToHost));
   HIPCHK(hipMemset(d, 0, bytes));
+  return 0;
+}
+#endif
+
+#ifdef PS_QTRACE
+// diagnostic (tools/queue_trace.py): the last time-sliced step's trace (host buffers). dims =
+// {chunks, grid}; items [chunks * n][QT_ITEM], exits [grid][QT_EXIT] (kernel_v2.inc, QT_*);
+// rank [n] = every env's position in order_kernel's order of that step. Null: not copied.
+int ps_debug_qtrace(ps_env* E, int32_t* dims, uint64_t* items, uint64_t* exits, int32_t* rank) {
+  if (!E || !E->qtrace) return fail("no time-sliced step in this handle");
+  GUARD(E);
+  HIPCHK(hipDeviceSynchronize());
+  const size_t ni = (size_t)E->n * E->chunks * QT_ITEM;
+  if (dims) dims[0] = E->chunks, dims[1] = qtrace_grid(E);
+  if (items) HIPCHK(hipMemcpy(items, E->qtrace, sizeof(uint64_t) * ni, hipMemcpyDeviceToHost));
+  if (exits)
+    HIPCHK(hipMemcpy(exits, E->qtrace + ni, sizeof(uint64_t) * qtrace_grid(E) * QT_EXIT, hipMemcpyDeviceToHost));
+  if (rank) HIPCHK(hipMemcpy(rank, E->qrank, sizeof(int) * E->n, hipMemcpyDeviceToHost));
   return 0;
 }
 #endif
