@@ -118,7 +118,7 @@ class TaskCfg(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_steps_lookahead", i32), ("fingering_reward", i32), ("forearm_reward", i32),
                 ("wrong_press_termination", i32), ("energy_penalty_coef", d),
                 ("solver_iterations", i32), ("max_contacts", i32), ("canonical_actions", i32),
-                ("solver", i32), ("randomize_hand_positions", i32), ("solver_refine", i32)]
+                ("solver", i32), ("randomize_hand_positions", i32), ("solver_refine", i32), ("hand_side", i32)]
 
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
@@ -155,6 +155,7 @@ class AugmentDesc(C.Structure):
 
 
 SOLVER_EXACT = SOLVER_NEWTON = 1
+HAND_BOTH, HAND_RIGHT, HAND_LEFT = 0, 1, 2  # ps_task_cfg.hand_side
 HAND_POSITION_OFFSET = 0.05  # piano_with_shadow_hands.py:46
 
 
@@ -167,6 +168,9 @@ def obs_joints(md: "ModelDesc" = None):
 
 def obs_dim(cfg: TaskCfg, md: "ModelDesc" = None) -> int:
     """goal (L+1)*89 + fingering 10 (if enabled) + piano/state 88 + sustain 1 + the joints_pos
-    entries of both hands (2*26 for the full hands)."""
-    return (cfg.n_steps_lookahead + 1) * (NKEY + 1) + (10 if cfg.fingering_reward else 0) \
-        + NKEY + 1 + sum(obs_joints(md))
+    entries of both hands (2*26 for the full hands). With ``cfg.hand_side`` (the one-hand task):
+    fingering 5, the kept hand's joints_pos only, then its root position 3."""
+    g = (cfg.n_steps_lookahead + 1) * (NKEY + 1) + NKEY + 1
+    if cfg.hand_side:
+        return g + (5 if cfg.fingering_reward else 0) + obs_joints(md)[cfg.hand_side - 1] + 3
+    return g + (10 if cfg.fingering_reward else 0) + sum(obs_joints(md))

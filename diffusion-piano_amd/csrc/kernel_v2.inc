@@ -137,6 +137,7 @@ struct Cfg {
   uint32_t env0;  // global id of this handle's env 0 (ps_set_env_offset): Philox draws keyed by global env
   int full_cpl;   // test hook (PIANOSIM_DEBUG_FULL_COUPLED): coupled substeps take the 28-column C block
   int refine;     // ps_task_cfg.solver_refine: 0 none, 1 a refining Newton step on coupled substeps, 2 all
+  int hand;       // ps_task_cfg.hand_side: 0 both hands; 1 right / 2 left only (the one-hand task layer)
 };
 
 struct Bufs {
@@ -1271,10 +1272,15 @@ __device__ __forceinline__ f3 key_target2(const DevModel* __restrict__ m, const 
   return c;
 }
 
+// The one-hand task (cfg.hand; piano_with_one_shadow_hand.py:297-345): the fingering row is 5
+// wide, the kept hand's fingers only (0-4 right, 5-9 left -> slot f - 5); joints_pos is the kept
+// hand's (obs_dof lists no other), and the row ends with `root`, the world position of that
+// hand's root body
 __device__ __forceinline__ void write_obs2(const DevModel* __restrict__ m, const Song& song, const Cfg& cfg, const Shared& S,
-                           int t_obs, float* __restrict__ obs, int lane) {
+                           int t_obs, float* __restrict__ obs, int lane, const f3 root) {
+  const bool one = cfg.hand != 0;
   int G = (cfg.lookahead + 1) * (NK + 1);
-  int o_f = G, o_s = G + (cfg.fingering ? 10 : 0);
+  int o_f = G, o_s = G + (cfg.fingering ? (one ? 5 : 10) : 0);
   for (int i = lane; i < cfg.obs_dim; i += 64) {
     float val;
     if (i < G) {
@@ -1287,12 +1293,19 @@ __device__ __forceinline__ void write_obs2(const DevModel* __restrict__ m, const
       for (int n = 0; n < song.count[t_obs]; n++) {
         int f = song.fingers[t_obs * PS_MAX_NOTES + n];
         int idx = f < 5 ? (f < 0 ? f + 5 : f) : f;
+        if (one) {
+          if ((f < 5) != (cfg.hand == 1)) continue;  // the other hand's note
+          if (f >= 5) idx = f - 5;
+        }
         if (idx == slot) val = 1.f;
       }
     } else if (i < o_s + NK) {
       val = S.knorm[i - o_s];
     } else if (i == o_s + NK) {
       val = S.sustain;
+    } else if (one && i >= cfg.obs_dim - 3) {
+      const int c = i - (cfg.obs_dim - 3);
+      val = c == 0 ? root.x : c == 1 ? root.y : root.z;
     } else {
       val = S.dx[m->obs_dof[i - o_s - NK - 1]][6];
     }
@@ -1737,8 +1750,15 @@ __device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__
   kinematics2<false, XG>(m, S, L, D, lane, hand_dy TPASS);
   collide2<XG, WPE>(m, S, cfg.maxcon, lane, L.c_r TPASS);
   key_state2(m, S, D, lane);
+  // the one-hand task's <rh|lh>_shadow_hand/position: the kept hand's root body (hands/base.py:
+  // 112-114); its lane is the body's (as site_world2)
+  f3 root = mk3(0, 0, 0);
+  if (cfg.hand) {
+    const int B = (cfg.hand - 1) * NB;
+    root = mk3(__shfl(D.o[0], B, 64), __shfl(D.o[1], B, 64), __shfl(D.o[2], B, 64));
+  }
   if (do_reset) {
-    write_obs2(m, song, cfg, S, 0, obs_e, lane);
+    write_obs2(m, song, cfg, S, 0, obs_e, lane, root);
     if (lane < NDT) {
       bufs.qpos[rowoff + NK + lane] = 0.f;
       bufs.qvel[rowoff + NK + lane] = 0.f;
@@ -1826,13 +1846,15 @@ __device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__
     bool rh = f < 5;
     int site = (rh ? 0 : 1) * PS_NFINGER + (rh ? (f < 0 ? f + 5 : f) : f - 5);
     float tx = __shfl(tip_own.x, site, 64), ty = __shfl(tip_own.y, site, 64), tz = __shfl(tip_own.z, site, 64);
-    if (lane < cnt) {
+    // the one-hand task: the kept hand's fingered notes only (piano_with_one_shadow_hand.py:244-275,
+    // 304-313)
+    if (lane < cnt && (!cfg.hand || rh == (cfg.hand == 1))) {
       ds = tolerance(norm3(key_target2(m, S, k) - mk3(tx, ty, tz)), 0.f, 0.01f, 0.1f);
       dc = 1.f;
     }
     float s = wave_sum(ds), c = wave_sum(dc);
     fing = c > 0.f ? s / c : 0.f;
-  } else {
+  } else if (!cfg.hand) {  // (the one-hand task has no OT term: slot 3 stays 0)
     // ot_fingering (piano_with_shadow_hands.py:333-369): goal keys by ballot (ps_create rejects
     // a song with more than PS_MAX_NOTES goal keys in a step, so the min below never binds),
     // the K x 10 distance matrix lane-parallel, the assignment on lane 0 with its work arrays
@@ -1886,7 +1908,7 @@ __device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__
   bool terminal = t_new == song.T;
   float disc = 1.f;
   if (!terminal && cfg.wrong_press && failure) { terminal = true; disc = 0.f; }
-  write_obs2(m, song, cfg, S, t_new < song.T ? t_new : t_new - 1, obs_e, lane);
+  write_obs2(m, song, cfg, S, t_new < song.T ? t_new : t_new - 1, obs_e, lane, root);
   if (lane < NDT) {
     bufs.qpos[rowoff + NK + lane] = D.q;
     bufs.qvel[rowoff + NK + lane] = D.v;

@@ -141,7 +141,8 @@ static void enclosing_capsule(const double (*v)[3], int n, float* out) {
   }
 }
 
-static int build_dev_model(const ps_model_desc* d, DevModel* m) {
+// hand_side (ps_task_cfg): with PS_HAND_RIGHT / PS_HAND_LEFT joints_pos lists the kept hand only.
+static int build_dev_model(const ps_model_desc* d, DevModel* m, int hand_side = PS_HAND_BOTH) {
   memset(m, 0, sizeof(*m));
   m->timestep = (float)d->timestep;
   m->nsub = d->n_substeps;
@@ -250,12 +251,17 @@ static int build_dev_model(const ps_model_desc* d, DevModel* m) {
     }
   m->n_obsj = 0;
   for (int h = 0; h < NH; h++) {
+    if (hand_side != PS_HAND_BOTH && h != hand_side - 1) continue;  // the one-hand task: the kept hand's
     const int nj = d->n_obs_joints[h] ? d->n_obs_joints[h] : ND;
     if (nj < 0 || nj > ND) return fail("n_obs_joints out of range");
+    // a detached hand (model.build_model(hand_side=), every dof locked) under the two-hand task:
+    // its joints_pos entries read its held zeros
+    bool detached = true;
+    for (int j = 0; j < ND; j++) detached = detached && d->dof_locked[h][j];
     for (int j = 0; j < nj; j++) {
       const int dof = d->dof_obs_order[h][j];
       if (dof < 0 || dof >= ND) return fail("dof_obs_order out of range");
-      if (d->dof_locked[h][dof]) return fail("joints_pos lists a locked dof");
+      if (d->dof_locked[h][dof] && !detached) return fail("joints_pos lists a locked dof");
       m->obs_dof[m->n_obsj++] = h * ND + dof;
     }
   }
@@ -554,12 +560,40 @@ static int launch_builder(ps_env* E, int mode, const uint8_t* mask, const int* f
 extern "C" {
 
 const char* ps_last_error(void) { return g_err.c_str(); }
-int ps_version(void) { return 4; }  // 4: ps_task_cfg.struct_size
+int ps_version(void) { return 5; }  // 4: ps_task_cfg.struct_size; 5: ps_task_cfg.hand_side
 int ps_model_desc_size(void) { return (int)sizeof(ps_model_desc); }
 int ps_obs_dim(const ps_task_cfg* cfg) {
   if (!cfg || cfg->struct_size != PS_TASK_CFG_SIZE)
     return fail("ps_task_cfg.struct_size != sizeof(ps_task_cfg): rebuild against include/pianosim.h");
+  if (cfg->hand_side != PS_HAND_BOTH)  // goal, fingering 5, piano/state, sustain, joints_pos, position
+    return (cfg->n_steps_lookahead + 1) * (NK + 1) + (cfg->fingering_reward ? 5 : 0) + NK + 1 + ND + 3;
   return (cfg->n_steps_lookahead + 1) * (NK + 1) + (cfg->fingering_reward ? 10 : 0) + NK + 1 + NH * ND;
+}
+
+// The one-hand task's model: the other hand fully detached (model.build_model(hand_side=)).
+static int check_detached(const ps_model_desc* d, int h) {
+  const std::string who = h ? "the left hand" : "the right hand";
+  auto hand_of = [](int g) { return g < NGT ? g / NG : (g - NGT) / NX; };
+  for (int j = 0; j < ND; j++)
+    if (!d->dof_locked[h][j]) return fail("hand_side: " + who + " is not detached (dof " + std::to_string(j) + " is not locked)");
+  for (int g = 0; g < NG; g++)
+    if (d->geom_body[h][g] >= 0) return fail("hand_side: " + who + " is not detached (capsule " + std::to_string(g) + ")");
+  for (int i = 0; i < NX; i++)
+    if (d->xgeom_type[h][i] != PS_GEOM_NONE)
+      return fail("hand_side: " + who + " is not detached (box / hull collider " + std::to_string(i) + ")");
+  if (d->n_action <= 0) return fail("hand_side: " + who + " is not detached (the model has the full action row)");
+  for (int a = 0; a < NA; a++)
+    if (d->act_column[h][a] >= 0) return fail("hand_side: " + who + " is not detached (actuator " + std::to_string(a) + ")");
+  for (int i = 0; i < d->n_cappairs && i < PS_MAX_CAPPAIRS; i++)
+    if (d->cappair[i][0] / NG == h || d->cappair[i][1] / NG == h)
+      return fail("hand_side: " + who + " is not detached (capsule pair " + std::to_string(i) + " names it)");
+  for (int i = 0; i < d->n_xpairs && i < PS_MAX_XPAIRS; i++) {
+    const int a = d->xpair[i][0], b = d->xpair[i][1];
+    if (a < 0 || b < 0 || a >= NCOLL || b >= NCOLL) continue;  // (build_dev_model refuses it)
+    if (hand_of(a) == h || hand_of(b) == h)
+      return fail("hand_side: " + who + " is not detached (collider pair " + std::to_string(i) + " names it)");
+  }
+  return 0;
 }
 
 #ifdef PS_QTRACE
@@ -581,6 +615,13 @@ int ps_create(const ps_model_desc* model, const ps_song_desc* song, const ps_tas
   if (cfg->solver_iterations < 0) return fail("negative solver_iterations");
   if (cfg->solver_refine < 0 || cfg->solver_refine > 2) return fail("solver_refine must be 0, 1 or 2");
   if (cfg->solver != PS_SOLVER_NEWTON) return fail("unknown solver (PS_SOLVER_NEWTON is the only one)");
+  if (cfg->hand_side != PS_HAND_BOTH && cfg->hand_side != PS_HAND_RIGHT && cfg->hand_side != PS_HAND_LEFT)
+    return fail("hand_side must be PS_HAND_BOTH, PS_HAND_RIGHT or PS_HAND_LEFT");
+  if (cfg->hand_side != PS_HAND_BOTH) {
+    if (cfg->randomize_hand_positions)
+      return fail("randomize_hand_positions is an option of the two-hand task: refused with hand_side");
+    if (check_detached(model, PS_HAND_LEFT - cfg->hand_side)) return -1;  // the other hand: 1 - (side - 1)
+  }
   for (int t = 0; t < song->T; t++) {
     if (song->count[t] < 0 || song->count[t] > PS_MAX_NOTES) return fail("bad note count");
     // the ot_fingering reward assigns the step's goal keys to fingertips in a table of
@@ -594,13 +635,14 @@ int ps_create(const ps_model_desc* model, const ps_song_desc* song, const ps_tas
   DeviceGuard guard_(device);
   if (!guard_.ok) return fail("hipSetDevice(" + std::to_string(device) + ") failed");
   DevModel* hm = new DevModel;
-  if (build_dev_model(model, hm)) { delete hm; return -1; }
+  if (build_dev_model(model, hm, cfg->hand_side)) { delete hm; return -1; }
   const bool has_x = hm->nx > 0 || hm->nxpairs > 0;
   ps_env* E = new ps_env();
   E->n = n_envs;
   E->device = device;
   E->cfg = *cfg;
-  E->obs_dim = ps_obs_dim(cfg) - NH * ND + hm->n_obsj;  // the model's joints_pos entries
+  // the model's joints_pos entries (the one-hand task: the kept hand's)
+  E->obs_dim = ps_obs_dim(cfg) - (cfg->hand_side != PS_HAND_BOTH ? ND : NH * ND) + hm->n_obsj;
   E->action_dim = hm->n_action;
   E->has_x = has_x;
   E->T = song->T;
@@ -784,18 +826,23 @@ static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask,
     song = Song{E->T, E->aug.goal, E->aug.count, E->aug.keys, E->aug.fingers, E->aug.T_cap, E->aug.T};
     if (launch_builder(E, mode == 1 ? AUG_RESET : AUG_STEP, mask, nullptr, nullptr, nullptr, stream)) return -1;
   }
-  Cfg cfg{E->cfg.n_steps_lookahead, E->cfg.fingering_reward, E->cfg.forearm_reward, E->cfg.wrong_press_termination,
+  // (the one-hand task has no forearm term: forearm_reward is ignored)
+  Cfg cfg{E->cfg.n_steps_lookahead, E->cfg.fingering_reward, E->cfg.hand_side != PS_HAND_BOTH ? 0 : E->cfg.forearm_reward,
+          E->cfg.wrong_press_termination,
           E->cfg.solver_iterations, E->cfg.max_contacts, E->obs_dim, E->cfg.canonical_actions,
           (float)E->cfg.energy_penalty_coef, E->cfg.randomize_hand_positions != 0,
           (uint32_t)E->seed, (uint32_t)(E->seed >> 32), (uint32_t)E->env_offset, E->full_cpl,
-          E->cfg.solver_refine};
+          E->cfg.solver_refine, E->cfg.hand_side};
   Bufs b{E->qpos, E->qvel, E->qws, E->ctrl, E->sustain, E->t_idx, E->last,
          E->applied_on ? E->applied : nullptr, E->terms, E->tips, E->ncon, E->mus_acc, E->mus_ep, E->mus_cnt,
          E->hand_dy, E->episode, E->stats, E->con_out, E->warnings, E->park};
   // the time-sliced step: a launch of more envs than resident slots (below that every env has a
   // slot of its own from the start and there is no second round to balance), or every step
   // when PIANOSIM_CHUNKS says so
-  const bool sliced = mode == 0 && E->chunks >= 2 && (E->chunks_forced || E->n > E->step_grid);
+  // (a one-hand handle, hand_side != 0, is sliced only when PIANOSIM_CHUNKS says so: on its short
+  // chunks the time-sliced step has left envs wrong)
+  const bool sliced = mode == 0 && E->chunks >= 2 &&
+                      (E->chunks_forced || (E->n > E->step_grid && E->cfg.hand_side == PS_HAND_BOTH));
   if (sliced) {
     const int cap = E->n * E->chunks, grid = E->n < E->step_grid ? E->n : E->step_grid;
     hipLaunchKernelGGL(order_kernel, dim3(1), dim3(ORDER_THREADS), 0, (hipStream_t)stream, E->stats, E->last, E->order,

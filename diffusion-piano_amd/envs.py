@@ -78,6 +78,14 @@ class BoundedArray(NamedTuple):
 
 
 # ---------------------------------------------------------------- task configuration
+class HandSide(str, enum.Enum):
+    """``robopianist.models.hands.HandSide`` for ``TaskConfig.hand_side``; the plain strings
+    "right" / "left" are accepted too."""
+
+    RIGHT = "right"
+    LEFT = "left"
+
+
 @dataclass
 class TaskConfig:
     """``PianoWithShadowHands`` keyword arguments (piano_with_shadow_hands.py:50-66) plus the
@@ -132,6 +140,21 @@ class TaskConfig:
     # the per-env song tables of an augmented handle may take this many bytes (488 per env and
     # row: DESIGN.md section 11); more is an error at create
     augmentation_max_bytes: int = 8 << 30
+    # PianoWithOneShadowHand (piano_with_one_shadow_hand.py): "right" / "left" (or a HandSide) keeps
+    # that hand only - the other is detached from the model. Action 23 (20 reduced); observations
+    # goal, fingering (5 wide), piano/state, piano/sustain_state, <rh|lh>_shadow_hand/joints_pos
+    # and /position; rewards key_press, sustain, energy and (with fingering) fingering - no OT
+    # term, no forearm term. None: PianoWithShadowHands.
+    hand_side: Optional[str] = None
+
+    def side(self) -> Optional[str]:
+        """hand_side as None, "right" or "left"."""
+        if self.hand_side is None:
+            return None
+        v = self.hand_side.value if isinstance(self.hand_side, HandSide) else self.hand_side
+        if v not in ("right", "left"):
+            raise ValueError(f"hand_side must be None, 'right' or 'left', got {self.hand_side!r}")
+        return v
 
     def lookahead(self) -> int:
         if self.n_seconds_lookahead is not None:
@@ -161,6 +184,10 @@ def compile_task(midi, cfg: TaskConfig, canonical_actions: bool = True):
     else:
         song = music.song_tables(initial_sequence(midi, cfg), cfg.control_timestep, cfg.initial_buffer_time)
     hand = None
+    side = cfg.side()
+    if side is not None and cfg.randomize_hand_positions:
+        raise ValueError("randomize_hand_positions is an option of the two-hand task: the one-hand task "
+                         "(hand_side) has none")
     if cfg.hand_xml is not None and cfg.primitive_fingertip_collisions is not None:
         raise ValueError("hand_xml and primitive_fingertip_collisions are exclusive: the MJCF names its colliders")
     if cfg.hand_xml is not None:
@@ -175,8 +202,9 @@ def compile_task(midi, cfg: TaskConfig, canonical_actions: bool = True):
                                gravity_compensation=cfg.gravity_compensation,
                                attachment_yaw=cfg.attachment_yaw,
                                reduced_action_space=cfg.reduced_action_space,
-                               forearm_dofs=cfg.forearm_dofs)
+                               forearm_dofs=cfg.forearm_dofs, hand_side=side)
     tc = abi.TaskCfg()
+    tc.hand_side = abi.HAND_BOTH if side is None else 1 + model_lib.HAND_SIDES[side]
     tc.n_steps_lookahead = cfg.lookahead()
     tc.fingering_reward = int(not cfg.disable_fingering_reward and song.has_fingering)
     tc.forearm_reward = int(not cfg.disable_forearm_reward)
@@ -198,15 +226,24 @@ def compile_task(midi, cfg: TaskConfig, canonical_actions: bool = True):
 
 def obs_layout(tc: abi.TaskCfg, md: Optional[abi.ModelDesc] = None) -> Dict[str, slice]:
     """Observation keys in the order the reference driver concatenates them
-    (parallelized_base_v2.py:122-131); joints_pos as wide as the model's hands (``md``)."""
+    (parallelized_base_v2.py:122-131); joints_pos as wide as the model's hands (``md``). The
+    one-hand task (``tc.hand_side``): fingering 5 wide, the kept hand's joints_pos, then its root
+    position (piano_with_one_shadow_hand.py:297-318, hands/base.py:112-114)."""
     out, o = {}, 0
     g = (tc.n_steps_lookahead + 1) * (abi.NKEY + 1)
     out["goal"] = slice(o, o + g); o += g
+    nf = 5 if tc.hand_side else 10
     if tc.fingering_reward:
-        out["fingering"] = slice(o, o + 10); o += 10
+        out["fingering"] = slice(o, o + nf); o += nf
     out["piano/state"] = slice(o, o + abi.NKEY); o += abi.NKEY
     out["piano/sustain_state"] = slice(o, o + 1); o += 1
     nj = abi.obs_joints(md)
+    if tc.hand_side:
+        h = tc.hand_side - 1
+        name = ("rh", "lh")[h] + "_shadow_hand"
+        out[name + "/joints_pos"] = slice(o, o + nj[h]); o += nj[h]
+        out[name + "/position"] = slice(o, o + 3); o += 3
+        return out
     out["rh_shadow_hand/joints_pos"] = slice(o, o + nj[0]); o += nj[0]
     out["lh_shadow_hand/joints_pos"] = slice(o, o + nj[1]); o += nj[1]
     return out
@@ -217,7 +254,7 @@ class BatchedPianoEnv:
     """N envs on one GPU; all tensors live in HBM (torch-ROCm)."""
 
     def __init__(self, num_envs: int, midi, task: Optional[TaskConfig] = None, device=None,
-                 canonical_actions: bool = True, seed: int = 0, env_offset: int = 0):
+                 canonical_actions: bool = True, seed: int = 0, env_offset: int = 0, _compiled=None):
         """``seed`` keys the per-env random draws (randomize_hand_positions); ``env_offset`` is the
         global id of env 0 when one job's envs are sharded over GPUs (sharding.EnvShard.start), so
         global env g draws the same values at any world size."""
@@ -229,7 +266,11 @@ class BatchedPianoEnv:
         self.task = task or TaskConfig()
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.num_envs = int(num_envs)
-        self.model_desc, self.song, self.task_cfg = compile_task(midi, self.task, canonical_actions)
+        if _compiled is not None:  # from_compiled: the caller's descriptors as they are
+            self.model_desc, self.song, self.task_cfg = _compiled
+            canonical_actions = bool(self.task_cfg.canonical_actions)
+        else:
+            self.model_desc, self.song, self.task_cfg = compile_task(midi, self.task, canonical_actions)
         self.canonical_actions = canonical_actions
         self.obs_dim = abi.obs_dim(self.task_cfg, self.model_desc)
         self.obs_slices = obs_layout(self.task_cfg, self.model_desc)
@@ -258,6 +299,20 @@ class BatchedPianoEnv:
         self.reward = torch.zeros(N, **f32)
         self.discount = torch.ones(N, **f32)
         self.step_type = torch.zeros(N, device=self.device, dtype=torch.uint8)
+
+    @classmethod
+    def from_compiled(cls, num_envs: int, md: abi.ModelDesc, song: music.SongTables, tc: abi.TaskCfg, device=None,
+                      seed: int = 0, env_offset: int = 0) -> "BatchedPianoEnv":
+        """A handle on ``compile_task``'s outputs as given - e.g. with a field of ``tc`` edited
+        (tests, studies). No augmentations: they need the song as notes."""
+        # .task restates what tc carries (the model's options are not recoverable from md)
+        task = TaskConfig(n_steps_lookahead=tc.n_steps_lookahead, wrong_press_termination=bool(tc.wrong_press_termination),
+                          disable_forearm_reward=not tc.forearm_reward, energy_penalty_coef=tc.energy_penalty_coef,
+                          randomize_hand_positions=bool(tc.randomize_hand_positions), solver_refine=tc.solver_refine,
+                          solver_iterations=tc.solver_iterations or None, max_contacts=tc.max_contacts,
+                          physics_timestep=md.timestep, control_timestep=md.timestep * md.n_substeps,
+                          hand_side={abi.HAND_BOTH: None, abi.HAND_RIGHT: "right", abi.HAND_LEFT: "left"}[tc.hand_side])
+        return cls(num_envs, song, task, device=device, seed=seed, env_offset=env_offset, _compiled=(md, song, tc))
 
     def _set_augmentations(self, midi) -> None:
         """TaskConfig.augmentations -> ps_set_augmentations: the bank (the initial song, then
@@ -515,7 +570,7 @@ class _EnvView:
 class VectorizedPianoEnv:
     """Drop-in for ``parallelized_base_v2.VectorizedPianoEnv`` (parallelized_base_v2.py:21-67).
 
-    ``reset()`` returns ``{key: [N, d]}``; ``step(actions[N, 45])`` (canonical [-1, 1], as
+    ``reset()`` returns ``{key: [N, d]}``; ``step(actions[N, 45])`` ([N, 23] with ``hand_side``) (canonical [-1, 1], as
     after the reference's per-env ``CanonicalSpecWrapper``) returns ``(obs, rewards, dones)``.
     With ``return_numpy=True`` the outputs are numpy arrays like the reference's; otherwise
     they are torch-ROCm tensors that never leave HBM. The task kwargs default to the ones

@@ -78,6 +78,7 @@ REDUCED_THUMB_RANGE = (0.0, 0.698132)
 FOREARM_DOFS = ("forearm_tx", "forearm_ty")
 FINGERTIP_OFFSET = 0.026  # shadow_hand.py:81-82
 THUMBTIP_OFFSET = 0.0275
+HAND_SIDES = {"right": 0, "left": 1}  # hand index (base.HandSide; tasks/base.py:116-135: right first)
 FOREARM_KP = 300.0  # shadow_hand.py:41-52
 FOREARM_TY_RANGE = (0.0, 0.06)
 
@@ -395,7 +396,8 @@ def _subtree_mass(bodies, root):
 def build_model(control_timestep: float = CONTROL_TIMESTEP, physics_timestep: float = PHYSICS_TIMESTEP,
                 hand_collisions: bool = True, hand: Optional[HandSpec] = None,
                 gravity_compensation: bool = False, attachment_yaw: float = ATTACHMENT_YAW,
-                reduced_action_space: bool = False, forearm_dofs=FOREARM_DOFS) -> abi.ModelDesc:
+                reduced_action_space: bool = False, forearm_dofs=FOREARM_DOFS,
+                hand_side: Optional[str] = None) -> abi.ModelDesc:
     """Compile the scene into a ``ps_model_desc``.
 
     ``hand``: the right hand to use (``mjcf.load_hand`` of a user MJCF); default the authored
@@ -415,7 +417,18 @@ def build_model(control_timestep: float = CONTROL_TIMESTEP, physics_timestep: fl
     order. A removed joint keeps its dof slot, locked at 0 (``dof_locked``: no force, row or
     Jacobian entry - MuJoCo's body without that joint), and leaves joints_pos and the action row
     (``n_obs_joints``, ``act_column``, ``n_action``).
+
+    ``hand_side`` ("right" | "left"; PianoWithOneShadowHand, piano_with_one_shadow_hand.py:96-102):
+    the other hand is detached - MuJoCo's model does not contain it. Its slots stay in the
+    descriptor, empty: every dof locked, no capsule (``geom_body`` -1) or box / hull collider
+    (``PS_GEOM_NONE``), no pair naming one of its colliders, no actuator (``act_column`` -1), so
+    ``n_action`` is the kept hand's actuators + 1. ``n_obs_joints`` of the detached hand stays 0:
+    the one-hand observation layout comes from ``ps_task_cfg.hand_side``, not from the model.
     """
+    if hand_side not in (None, "right", "left"):
+        raise ValueError(f"hand_side must be None, 'right' or 'left', got {hand_side!r}")
+    keep = None if hand_side is None else HAND_SIDES[hand_side]
+    detached = [keep is not None and h != keep for h in range(abi.NHAND)]
     forearm_dofs = tuple(forearm_dofs)
     if any(f not in FOREARM_DOFS for f in forearm_dofs) or list(forearm_dofs) != [f for f in FOREARM_DOFS
                                                                                    if f in forearm_dofs]:
@@ -498,6 +511,8 @@ def build_model(control_timestep: float = CONTROL_TIMESTEP, physics_timestep: fl
         for g in range(abi.HAND_NGEOM):
             m.geom_body[h][g] = -1  # unused slot
         for g, geom in enumerate(geoms):
+            if detached[h]:
+                break  # a detached hand has no collider
             m.geom_body[h][g] = geom.body
             m.geom_pos[h][g][:] = _mirror_vec(geom.pos) if mir else geom.pos
             m.geom_axis[h][g][:] = _mirror_vec(geom.axis) if mir else geom.axis
@@ -510,13 +525,14 @@ def build_model(control_timestep: float = CONTROL_TIMESTEP, physics_timestep: fl
             m.tendon_dof[h][t][:] = (d2, d1)
             m.tendon_coef[h][t][:] = tcoef[t]
         # removed joints (reduced_action_space, forearm_dofs): locked dof slots
+        # (and every joint of a detached hand)
         locked = [(reduced_action_space and any(dof.name.endswith(x) for x in REDUCED_ACTION_SPACE_EXCLUDED))
-                  or (dof.name in FOREARM_DOFS and dof.name not in forearm_dofs) for dof in dofs]
+                  or (dof.name in FOREARM_DOFS and dof.name not in forearm_dofs) or detached[h] for dof in dofs]
         for j, dof in enumerate(dofs):
             m.dof_locked[h][j] = int(locked[j])
             if reduced_action_space and dof.name.endswith("THJ2"):
                 m.dof_range[h][j][:] = REDUCED_THUMB_RANGE
-        if any(locked):
+        if any(locked) and not detached[h]:
             oo = [j for j in obs_order if not locked[j]]
             m.n_obs_joints[h] = len(oo)
             for i in range(abi.HAND_NDOF):
@@ -537,7 +553,7 @@ def build_model(control_timestep: float = CONTROL_TIMESTEP, physics_timestep: fl
         col = 0
         for h in range(abi.NHAND):
             for a, (kind, target, *_) in enumerate(acts):
-                present = kind == 1 or not m.dof_locked[h][target]
+                present = (kind == 1 or not m.dof_locked[h][target]) and not detached[h]
                 m.act_column[h][a] = col if present else -1
                 col += present
         m.n_action = col + 1
@@ -549,6 +565,8 @@ def build_model(control_timestep: float = CONTROL_TIMESTEP, physics_timestep: fl
         mir = h == 1
         nv = 0
         for i, xg in enumerate(xgeoms):
+            if detached[h]:
+                break
             m.xgeom_type[h][i] = abi.GEOM_BOX if xg.kind == "box" else abi.GEOM_HULL
             m.xgeom_body[h][i] = xg.body
             m.xgeom_pos[h][i][:] = _mirror_vec(xg.pos) if mir else xg.pos
@@ -568,11 +586,15 @@ def build_model(control_timestep: float = CONTROL_TIMESTEP, physics_timestep: fl
                 nv += len(v)
     set_const(m)
     pairs = capsule_pairs(bodies, geoms, excludes) if hand_collisions else []
+    if keep is not None:  # same-hand pairs of the kept hand only
+        pairs = [p for p in pairs if all(collider_hand(g) == keep for g in p)]
     assert len(pairs) <= abi.MAX_CAPPAIRS
     m.n_cappairs = len(pairs)
     for i, (a, b) in enumerate(pairs):
         m.cappair[i][:] = (a, b)
     xpairs = extra_pairs(bodies, geoms, xgeoms, excludes) if hand_collisions else []
+    if keep is not None:
+        xpairs = [p for p in xpairs if all(collider_hand(g) == keep for g in p)]
     if len(xpairs) > abi.MAX_XPAIRS:
         raise ValueError(f"{len(xpairs)} collider pairs with a box/hull collider; at most {abi.MAX_XPAIRS}")
     m.n_xpairs = len(xpairs)
@@ -642,7 +664,8 @@ def set_const(m: abi.ModelDesc) -> None:
             M += m.body_mass[h][b] * Jp[b].T @ Jp[b] + Jr[b].T @ Iw @ Jr[b]
         free = [j for j in range(nd) if not m.dof_locked[h][j]]  # a removed joint: not in M
         Minv = np.zeros((nd, nd))
-        Minv[np.ix_(free, free)] = np.linalg.inv(M[np.ix_(free, free)])
+        if free:  # (a detached hand has none)
+            Minv[np.ix_(free, free)] = np.linalg.inv(M[np.ix_(free, free)])
         for b in range(nb):
             m.body_invweight[h][b] = float(np.trace(Jp[b] @ Minv @ Jp[b].T)) / 3.0
         for j in range(nd):
@@ -671,6 +694,12 @@ def capsule_pairs(bodies, geoms, excludes):
         for b in range(ng):
             pairs.append((a, stride + b))
     return pairs
+
+
+def collider_hand(g: int) -> int:
+    """The hand of a global collider id (capsule h*HAND_NGEOM + g, extra 2*HAND_NGEOM + h*HAND_NXGEOM + i)."""
+    ng = abi.NHAND * abi.HAND_NGEOM
+    return g // abi.HAND_NGEOM if g < ng else (g - ng) // abi.HAND_NXGEOM
 
 
 def extra_pairs(bodies, geoms, xgeoms, excludes):

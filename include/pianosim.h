@@ -197,7 +197,7 @@ typedef struct {
 /* Task options (piano_with_shadow_hands.py:50-66). The first field is the struct's size: a
  * caller sets struct_size = sizeof(ps_task_cfg) (= PS_TASK_CFG_SIZE of the header it was built
  * against) and ps_create / ps_obs_dim refuse any other value - a caller built against an older
- * header (before ps_version 4: no struct_size, no solver_refine) fails with "rebuild against
+ * header (before ps_version 4: no struct_size, no solver_refine; before 5: no hand_side) fails with "rebuild against
  * include/pianosim.h" instead of the library reading past the end of its struct. */
 typedef struct {
   uint32_t struct_size;             /* sizeof(ps_task_cfg) */
@@ -222,6 +222,19 @@ typedef struct {
                                        ~1.5e-4 -> ~8e-5 on coupled states) at ~5% of the throughput
                                        (DESIGN.md section 5). A solve that ends in the previous
                                        substep's guessed piece (one checked step) is not refined. */
+  int32_t hand_side;                /* PS_HAND_BOTH: PianoWithShadowHands. PS_HAND_RIGHT / PS_HAND_LEFT:
+                                       PianoWithOneShadowHand (piano_with_one_shadow_hand.py) with that
+                                       hand; the model's other hand must be detached (every dof locked,
+                                       no collider, no pair, no actuator: model.build_model(hand_side=)).
+                                       Observation row: goal, fingering (5 wide, the kept hand's fingers,
+                                       only with fingering_reward), piano/state, sustain, the kept hand's
+                                       joints_pos, then the world position of its root (forearm) body, 3.
+                                       Rewards: key_press, sustain, energy over the kept hand's actuators
+                                       and, with fingering_reward, the fingering term over the kept hand's
+                                       fingered notes (0 with none); no OT term (slot 3 is 0 without
+                                       fingering_reward) and no forearm term (forearm_reward is ignored).
+                                       randomize_hand_positions is refused. ps_fingertips keeps its shape:
+                                       the detached hand's rows are its rest pose and mean nothing. */
 } ps_task_cfg;
 #define PS_TASK_CFG_SIZE ((uint32_t)sizeof(ps_task_cfg))
 
@@ -232,6 +245,9 @@ typedef struct {
  * to. The round-1 truncated PGS (value 0) is retired; ps_create rejects it. */
 #define PS_SOLVER_EXACT 1
 #define PS_SOLVER_NEWTON 1
+#define PS_HAND_BOTH 0
+#define PS_HAND_RIGHT 1
+#define PS_HAND_LEFT 2
 #define PS_HAND_POSITION_OFFSET 0.05  /* piano_with_shadow_hands.py:46 _POSITION_OFFSET */
 
 #define PS_MAX_CONTACTS_LIMIT 24
@@ -290,7 +306,9 @@ typedef struct ps_env ps_env;
 
 const char* ps_last_error(void);
 int ps_version(void);
-int ps_obs_dim(const ps_task_cfg* cfg);  /* the full hand (n_obs_joints = PS_HAND_NDOF) */
+/* the full hand (n_obs_joints = PS_HAND_NDOF); with cfg->hand_side the one-hand row:
+ * (L+1)*89 + (5 if fingering) + 88 + 1 + 26 + 3 */
+int ps_obs_dim(const ps_task_cfg* cfg);
 /* sizeof(ps_model_desc), for host-side layout checks. */
 int ps_model_desc_size(void);
 
