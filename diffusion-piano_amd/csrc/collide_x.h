@@ -82,73 +82,8 @@ __device__ __forceinline__ f3 nrmz3(f3 a) {
   return n > 0.f ? a * (1.f / n) : a;
 }
 
-// Support cells of a hull (DevModel::x_cell): for each cube-map cell of the direction sphere
-// (face 2 ax + (d_ax < 0), cell (i, j) of the tangent ratios d_(ax+1) / |d_ax|, d_(ax+2) / |d_ax|
-// over [-1, 1], as hull_cell in collide_x.h) the cone over the cell grown by 0.02 in the ratios,
-// spanned by its 4 corner rays c_k. A vertex v is dropped when one vertex u beats it at every
-// corner by more than 1e-5 of the hull's extent: (u - v).c_k > tol for all k holds for every
-// direction in the cone (a non-negative combination of the c_k), and the margin is far above
-// fp32 rounding of the dots, so v never is the fp32 maximum there either. The fp32 scan over
-// the rest returns the first maximal vertex of the full scan.
-inline void hull_support_cells(const double (*v)[3], int n, uint64_t* out) {
-  double ext = 0.0;
-  for (int i = 0; i < n; i++) ext = fmax(ext, sqrt(v[i][0] * v[i][0] + v[i][1] * v[i][1] + v[i][2] * v[i][2]));
-  const double tol = 1e-5 * ext, grow = 0.02;
-  for (int face = 0; face < 6; face++)
-    for (int ci = 0; ci < XCG; ci++)
-      for (int cj = 0; cj < XCG; cj++) {
-        const int ax = face / 2;
-        const double sg = face % 2 ? -1.0 : 1.0;
-        double c[4][3];
-        for (int k = 0; k < 4; k++) {
-          const double a = -1.0 + 2.0 * (ci + (k & 1)) / XCG + ((k & 1) ? grow : -grow);
-          const double b = -1.0 + 2.0 * (cj + (k >> 1)) / XCG + ((k >> 1) ? grow : -grow);
-          c[k][ax] = sg;
-          c[k][(ax + 1) % 3] = a;
-          c[k][(ax + 2) % 3] = b;
-        }
-        double P[PS_HULL_MAXVERT][4];
-        for (int i = 0; i < n; i++)
-          for (int k = 0; k < 4; k++) P[i][k] = v[i][0] * c[k][0] + v[i][1] * c[k][1] + v[i][2] * c[k][2];
-        uint64_t mask = 0;
-        for (int i = 0; i < n; i++) {
-          bool dominated = false;
-          for (int u = 0; u < n && !dominated; u++) {
-            if (u == i) continue;
-            bool all = true;
-            for (int k = 0; k < 4 && all; k++) all = P[u][k] - P[i][k] > tol;
-            dominated = all;
-          }
-          if (!dominated) mask |= 1ull << i;
-        }
-        out[(face * XCG + ci) * XCG + cj] = mask;
-      }
-}
-
-// The support-cell vertex table of a hull (DevModel::x_cellv) from its cells' masks: per cell the
-// candidates' fp32 coordinates in ascending vertex order, padded with the last candidate (a
-// repeat never wins the first-maximal search), and cell XNCELL = vertex 0 (the zero direction).
-// false when a cell holds more than XCV candidates (or none): the mask scan is used instead.
-inline bool hull_cell_table(const double (*v)[3], const uint64_t* cells, float (*out)[XCV][4]) {
-  for (int c = 0; c <= XNCELL; c++) {
-    uint64_t msk = c < XNCELL ? cells[c] : 1ull;
-    const int cnt = __builtin_popcountll(msk);
-    if (cnt < 1 || cnt > XCV) return false;
-    int k = 0, last = 0;
-    while (msk) {
-      last = __builtin_ctzll(msk);
-      msk &= msk - 1ull;
-      for (int j = 0; j < 3; j++) out[c][k][j] = (float)v[last][j];
-      out[c][k++][3] = 0.f;
-    }
-    for (; k < XCV; k++)
-      for (int j = 0; j < 4; j++) out[c][k][j] = out[c][k - 1][j];
-  }
-  return true;
-}
-
 // support cell of a (local) direction: the cube-map face of its largest component, the cell of
-// its two tangent ratios over [-1, 1] (hull_support_cells above builds the tables with
+// its two tangent ratios over [-1, 1] (hull_support_cells of model_build.h builds the tables with
 // the same convention; its cells are grown, so rounding at a cell edge picks a cell that still
 // holds the direction). Clamped: any input (NaN included) gives a valid cell.
 __device__ __forceinline__ int hull_cell(f3 d) {

@@ -1,6 +1,6 @@
 // Device-side model tables for the pianosim kernels (float, flattened, plus the
 // topology tables the wave-cooperative phases iterate over). Built on the host from a
-// ps_model_desc by build_dev_model() in pianosim.hip.
+// ps_model_desc by build_dev_model() in model_build.h.
 #pragma once
 #include <stdint.h>
 

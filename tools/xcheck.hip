@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../diffusion-piano_amd/csrc/devmodel.h"
+#include "../diffusion-piano_amd/csrc/model_build.h"  // hull_support_cells, hull_cell_table
 #include "../diffusion-piano_amd/csrc/prims.h"
 #include "../diffusion-piano_amd/csrc/collide_x.h"
 
