@@ -18,7 +18,7 @@ EXPORTS = (
     "ps_fingertips", "ps_contact_count", "ps_musical_metrics", "ps_solver_stats", "ps_get_hand_offset",
     "ps_set_hand_offset", "ps_record_contacts", "ps_contacts", "ps_set_env_offset", "ps_warnings",
     "ps_env_obs_dim", "ps_env_action_dim", "ps_episode_returns", "ps_set_augmentations", "ps_get_augmentation",
-    "ps_set_augmentation", "ps_get_song_tables",
+    "ps_set_augmentation", "ps_get_song_tables", "ps_record_midi", "ps_midi_events", "ps_midi_push",
 )
 
 # Every entry point declared in include/pianorl.h.
@@ -76,6 +76,10 @@ def load() -> C.CDLL:
         L.ps_episode_returns.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     if hasattr(L, "ps_set_env_offset"):
         L.ps_set_env_offset.argtypes = [vp, C.c_int64]
+    if hasattr(L, "ps_record_midi"):
+        L.ps_record_midi.argtypes = [vp, i32, u64]
+        L.ps_midi_events.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+        L.ps_midi_push.argtypes = [vp, vp, i32, vp]
     for name, argc in (("ps_set_augmentations", 2), ("ps_get_augmentation", 7), ("ps_set_augmentation", 5),
                        ("ps_get_song_tables", 6), ("ps_solver_stats", 3), ("ps_get_hand_offset", 4), ("ps_set_hand_offset", 3),
                        ("ps_contacts", 3), ("ps_warnings", 3), ("ps_env_obs_dim", 1), ("ps_env_action_dim", 1)):
@@ -142,7 +146,7 @@ SONG_LIB_PATH = Path(os.environ.get("PIANOSONG_LIB", HERE / "libpianosong.so"))
 # Every entry point declared in include/pianosong.h.
 SONG_EXPORTS = ("pss_last_error", "pss_version", "pss_parse_midi", "pss_from_notes", "pss_free", "pss_info",
                 "pss_get", "pss_add_fingering", "pss_trim_silence", "pss_song_tables", "pss_stretch", "pss_transpose",
-                "pss_flatten", "pss_build_tables", "pss_draw_augmentation")
+                "pss_flatten", "pss_build_tables", "pss_draw_augmentation", "pss_write_smf")
 _song = None
 
 
@@ -173,9 +177,11 @@ def load_song() -> C.CDLL:
     L.pss_build_tables.argtypes = [vp, f64, i32, f64, f64, i32, vp, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
     L.pss_draw_augmentation.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, vp, i32, vp, i32, C.POINTER(i32),
                                         C.POINTER(f64), C.POINTER(i32)]
+    L.pss_write_smf.argtypes = [vp, vp, C.c_size_t]
     for name in SONG_EXPORTS[2:]:
         if name != "pss_free":
             getattr(L, name).restype = i32
+    L.pss_write_smf.restype = C.c_int64
     _song = L
     return L
 

@@ -30,6 +30,10 @@ NWARN = 3  # ps_warnings slots: mj_checkPos / mj_checkVel / mj_checkAcc resets
 WARN_BADQPOS, WARN_BADQVEL, WARN_BADQACC = range(3)
 NMUSIC = 6  # ps_musical_metrics slots: precision, recall, f1, sustain_precision, sustain_recall, sustain_f1
 FIRST, MID, LAST = 0, 1, 2
+KEY_THRESHOLD = 0.00872665  # piano.py:31 _KEY_THRESHOLD: a key within this of its lower stop is active
+SUSTAIN_THRESHOLD = 0.5     # piano.py:32
+# one event word of the MIDI recorder (PS_MIDI_*): note | kind << 8 | substep ordinal << 10
+MIDI_NOTE_ON, MIDI_NOTE_OFF, MIDI_SUSTAIN_ON, MIDI_SUSTAIN_OFF = range(4)
 
 d = C.c_double
 i32 = C.c_int32

@@ -156,7 +156,15 @@ struct Bufs {
   Contact* con_out;  // [N][MAXCON] contacts of the last step (ps_record_contacts), or null
   int* warnings;     // [N][PS_NWARN] mj_checkPos / Vel / Acc resets since create
   float* park;       // [N][PARK_WORDS][64] lane state parked around the Newton solve
+  uint32_t* keybits; // [N][KB_HDR + nsub * KB_ROW] the MIDI recorder's capture (ps_record_midi), or null
 };
+// The MIDI recorder's capture row of one env (midi_events.inc reads it after the launch): a header
+// word - the number of valid substep rows of this launch, or KB_NEW_EPISODE with none - then one
+// row per substep of the control step: the 88 key activations (key k = bit k & 31 of word k >> 5)
+// and the sustain activation (bit KB_SUSTAIN_BIT of word 2) at the end of that substep.
+constexpr int KB_HDR = 1, KB_ROW = 3, KB_SUSTAIN_BIT = 24;
+constexpr uint32_t KB_NEW_EPISODE = 0x80000000u;
+__device__ __forceinline__ size_t kb_stride(int nsub) { return (size_t)(KB_HDR + nsub * KB_ROW); }
 // LaneDyn words that outlive the constraint solve but are not used by it (the factor of
 // M + hD for the integration, the warm-start and key force terms): parked in the env's row of
 // bufs.park (L2-resident while in use) so their registers are free during the solve
@@ -1712,6 +1720,28 @@ __device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__
         }
       }
       wsync();
+      if (bufs.keybits) {
+        // the recorder's capture: key_state2's activation rule on this substep's key angles.
+        // Nothing is kept for it: a later chunk of the step writes its own rows, and a substep
+        // that mj_checkAcc redoes gets here once
+        uint64_t kb[2];
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+          const int k = lq + 64 * j;
+          bool act = false;
+          if (k < NK) {
+            const float khi = mq->key_hi[k];
+            act = fabsf(clampf(D.kq[j], mq->key_lo[k], khi) - khi) <= KEY_THRESHOLD;
+          }
+          kb[j] = __ballot(act);
+        }
+        if (lq == 0) {
+          uint32_t* row = bufs.keybits + (size_t)e * kb_stride(mq->nsub) + KB_HDR + s * KB_ROW;
+          row[0] = (uint32_t)kb[0];
+          row[1] = (uint32_t)(kb[0] >> 32);
+          row[2] = ((uint32_t)kb[1] & 0xffffffu) | (S.sustain >= SUSTAIN_THRESHOLD ? 1u << KB_SUSTAIN_BIT : 0u);
+        }
+      }
       TSTAMP(6);
 #ifdef PS_TIMING
       if (lq == 0) { tacc[9] += 52 + 4 * S.ncon; tacc[10] += S.ncon; }
@@ -1782,6 +1812,7 @@ __device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__
       bufs.t_idx[e] = 0;
       bufs.last[e] = 0;
       bufs.ncon[e] = S.ncon;
+      if (bufs.keybits) bufs.keybits[(size_t)e * kb_stride(m->nsub)] = KB_NEW_EPISODE;
       if (mode == 0) {
         reward[e] = 0.f;
         discount[e] = 1.f;
@@ -1951,6 +1982,7 @@ __device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__
     bufs.t_idx[e] = t_new;
     bufs.last[e] = terminal ? 1 : 0;
     bufs.ncon[e] = S.ncon;
+    if (bufs.keybits) bufs.keybits[(size_t)e * kb_stride(m->nsub)] = (uint32_t)m->nsub;
   }
   if (bufs.con_out) {  // inspection copy of the contact list (ps_contacts)
     constexpr int CW = (int)(sizeof(Contact) / sizeof(int));

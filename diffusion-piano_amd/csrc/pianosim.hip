@@ -25,6 +25,7 @@ using namespace ps;
 
 #include "kernel_v2.inc"
 #include "augment.inc"
+#include "midi_events.inc"
 
 // ------------------------------------------------------------------ host side
 static thread_local std::string g_err;
@@ -106,9 +107,15 @@ struct ps_env {
   bool aug_on;
   AugDev aug;
   size_t aug_lds;
+  // the MIDI recorder (ps_record_midi): the step kernel's capture rows [N][KB_HDR + nsub * KB_ROW]
+  // (null: not recording), the event banks and per-env words behind them
+  int nsub;
+  uint32_t* keybits;
+  MidiRec midi;
   // the device allocations: the handle's own (freed with it), the augmentation bank's (replaced
-  // by ps_set_augmentations), con_out (switched by ps_record_contacts)
-  DevMem mem, aug_mem, con_mem;
+  // by ps_set_augmentations), con_out (switched by ps_record_contacts), the MIDI recorder's
+  // (replaced or freed by ps_record_midi)
+  DevMem mem, aug_mem, con_mem, midi_mem;
 };
 
 // Every entry point that touches device memory or launches binds the handle's device for its
@@ -148,10 +155,19 @@ static int launch_builder(ps_env* E, int mode, const uint8_t* mask, const int* f
   return 0;
 }
 
+// the recorder's compaction, after the step / reset kernel that wrote the capture rows
+static int launch_midi(ps_env* E, void* stream) {
+  const size_t stride = (size_t)KB_HDR + (size_t)E->nsub * KB_ROW;
+  hipLaunchKernelGGL(midi_events_kernel, dim3(E->n), dim3(64), 0, (hipStream_t)stream, E->midi,
+                     (const uint32_t*)E->keybits + KB_HDR, stride, E->keybits, stride, 0, E->n);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 extern "C" {
 
 const char* ps_last_error(void) { return g_err.c_str(); }
-int ps_version(void) { return 5; }  // 4: ps_task_cfg.struct_size; 5: ps_task_cfg.hand_side
+int ps_version(void) { return 6; }  // 4: ps_task_cfg.struct_size; 5: ps_task_cfg.hand_side; 6: ps_record_midi
 int ps_model_desc_size(void) { return (int)sizeof(ps_model_desc); }
 int ps_obs_dim(const ps_task_cfg* cfg) {
   std::string err;
@@ -187,6 +203,7 @@ int ps_create(const ps_model_desc* model, const ps_song_desc* song, const ps_tas
   E->action_dim = hm->n_action;
   E->has_x = hm->nx > 0 || hm->nxpairs > 0;
   E->T = song->T;
+  E->nsub = model->n_substeps;
   E->seed = seed;
   const size_t N = (size_t)n_envs, T = (size_t)song->T;
   DevMem& mem = E->mem;
@@ -357,6 +374,7 @@ static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask,
   b.mus_acc = E->mus_acc; b.mus_ep = E->mus_ep; b.mus_cnt = E->mus_cnt; b.hand_dy = E->hand_dy;
   b.episode = E->episode; b.stats = E->stats; b.con_out = E->con_out; b.warnings = E->warnings; b.park = E->park;
   b.applied = E->applied_on ? E->applied : nullptr;
+  b.keybits = E->keybits;
   // the time-sliced step: a launch of more envs than resident slots (below that every env has a
   // slot of its own from the start and there is no second round to balance), or every step
   // when PIANOSIM_CHUNKS says so
@@ -384,7 +402,7 @@ static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask,
 #undef PS_LAUNCH_Q
 #endif
     HIPCHK(hipGetLastError());
-    return 0;
+    return E->keybits ? launch_midi(E, stream) : 0;
   }
   const int* order = nullptr;
   if (mode == 0 && E->ordered && E->n >= 2048) {  // below one wave of workgroups there is no tail to balance
@@ -406,7 +424,7 @@ static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask,
   }
 #undef PS_LAUNCH
   HIPCHK(hipGetLastError());
-  return 0;
+  return E->keybits ? launch_midi(E, stream) : 0;
 }
 
 int ps_reset(ps_env* E, const uint8_t* env_mask, float* obs, void* stream) {
@@ -679,6 +697,65 @@ int ps_get_song_tables(ps_env* E, float* goal, int32_t* count, int32_t* keys, in
   return -(copy_dd(goal, E->aug.goal, rows * (NK + 1), stream) || copy_dd(count, E->aug.count, rows, stream) ||
            copy_dd(keys, E->aug.keys, rows * PS_MAX_NOTES, stream) ||
            copy_dd(fingers, E->aug.fingers, rows * PS_MAX_NOTES, stream));
+}
+
+int ps_record_midi(ps_env* E, int max_events, uint64_t max_bytes) {
+  if (!E) return fail("null env");
+  if (max_events < 0 || max_events > (1 << 24)) return fail("ps_record_midi: max_events outside 0 .. 2^24");
+  // (a request over the budget is refused before anything changes: a recording handle goes on
+  // recording into the banks it has)
+  const size_t N = (size_t)E->n, kb = (size_t)KB_HDR + (size_t)E->nsub * KB_ROW;
+  const size_t per_env = sizeof(uint32_t) * (2 * (size_t)max_events + kb) + sizeof(int) * MS_WORDS;
+  if (max_events && max_bytes && N * per_env > max_bytes)
+    return fail("ps_record_midi: the recorder needs " + std::to_string(N * per_env) + " B (" + std::to_string(E->n) +
+                " envs x (2 banks x " + std::to_string(max_events) + " events x 4 B + " +
+                std::to_string(sizeof(uint32_t) * kb + sizeof(int) * MS_WORDS) + " B)), over the budget of " +
+                std::to_string(max_bytes) + " B");
+  GUARD(E);
+  HIPCHK(hipDeviceSynchronize());  // (init-time: nothing that reads the old buffers is in flight)
+  E->midi_mem.clear();
+  E->keybits = nullptr;
+  E->midi = MidiRec{};
+  if (!max_events) return 0;
+  MidiRec r{};
+  uint32_t* kbits = nullptr;
+  r.max_events = max_events;
+  hipError_t e = E->midi_mem.alloc(r.events, N * 2 * (size_t)max_events, true);
+  if (e == hipSuccess) e = E->midi_mem.alloc(r.state, N * MS_WORDS, true);
+  if (e == hipSuccess) e = E->midi_mem.alloc(kbits, N * kb, true);
+  if (e != hipSuccess) {
+    E->midi_mem.clear();
+    return fail(std::string("ps_record_midi: ") + hipGetErrorString(e));
+  }
+  HIPCHK(hipDeviceSynchronize());
+  E->midi = r;
+  E->keybits = kbits;
+  return 0;
+}
+
+int ps_midi_events(ps_env* E, int which, uint32_t* events, int32_t* count, int32_t* dropped, int32_t* substeps,
+                   void* stream) {
+  if (!E) return fail("null env");
+  if (!E->keybits) return fail("MIDI recording is off (ps_record_midi)");
+  if (which != 0 && which != 1) return fail("ps_midi_events: which is 0 (the running episode) or 1 (the last finished one)");
+  GUARD(E);
+  hipLaunchKernelGGL(midi_gather_kernel, dim3(E->n), dim3(256), 0, (hipStream_t)stream, E->midi, which, events, count,
+                     dropped, substeps, E->n);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ps_midi_push(ps_env* E, const uint32_t* bits, int rows, void* stream) {
+  if (!E || !bits) return fail("null argument");
+  if (!E->keybits) return fail("MIDI recording is off (ps_record_midi)");
+  if (rows < 1 || rows > E->nsub)
+    return fail("ps_midi_push: " + std::to_string(rows) + " rows; one push takes 1 .. " + std::to_string(E->nsub) +
+                " (the handle's substeps per step)");
+  GUARD(E);
+  hipLaunchKernelGGL(midi_events_kernel, dim3(E->n), dim3(64), 0, (hipStream_t)stream, E->midi, bits,
+                     (size_t)rows * KB_ROW, (uint32_t*)nullptr, (size_t)0, rows, E->n);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 int ps_set_env_offset(ps_env* E, int64_t global_first_env) {

@@ -240,7 +240,7 @@ bool to_int(const std::string& s, long* out) {
 extern "C" {
 
 const char* pss_last_error(void) { return g_err.c_str(); }
-int pss_version(void) { return 1; }
+int pss_version(void) { return 2; }  // 2: pss_write_smf
 
 int pss_parse_midi(const uint8_t* data, size_t len, pss_seq** out) {
   if (!data || !out) return fail("pss_parse_midi: null argument");
@@ -543,6 +543,82 @@ int pss_draw_augmentation(uint64_t seed, uint32_t env, uint32_t episode, const p
   psb::draw((uint32_t)seed, (uint32_t)(seed >> 32), env, episode, reinterpret_cast<const psb::Var*>(vars), n_vars,
             reinterpret_cast<const psb::Song*>(bank), n_songs, song, factor, shift);
   return 0;
+}
+
+// Format 0, one track, SMF_DIVISION ticks per quarter note at SMF_TEMPO us per quarter note:
+// 2000 ticks per second, so a 5 ms physics substep is 10 ticks and a time on the substep grid
+// is written exactly.
+int64_t pss_write_smf(const pss_seq* s, uint8_t* out, size_t capacity) {
+  if (!s) return fail("pss_write_smf: null sequence");
+  constexpr int SMF_DIVISION = 1000, SMF_TEMPO = 500000;
+  constexpr double TICKS_PER_S = SMF_DIVISION * 1e6 / SMF_TEMPO;
+  constexpr double MAX_TICK = 268435455.0;  // the largest variable-length quantity (0x0FFFFFFF)
+  struct Msg {
+    int64_t tick;
+    int rank;  // at one tick: note-offs, control changes, note-ons
+    uint8_t b[3];
+  };
+  std::vector<Msg> ev;
+  ev.reserve(2 * s->notes.size() + s->ccs.size());
+  auto to_tick = [&](double t, int64_t* tick) {
+    if (!(t >= 0) || !(t * TICKS_PER_S <= MAX_TICK)) return false;
+    *tick = (int64_t)llround(t * TICKS_PER_S);
+    return true;
+  };
+  for (auto& n : s->notes) {
+    if (n.pitch < 0 || n.pitch > 127) return fail("pss_write_smf: pitch " + std::to_string(n.pitch) + " outside 0..127");
+    if (n.velocity < 0 || n.velocity > 127)
+      return fail("pss_write_smf: velocity " + std::to_string(n.velocity) + " outside 0..127");
+    int64_t t0, t1;
+    if (!to_tick(n.start_time, &t0) || !to_tick(n.end_time, &t1) || n.end_time < n.start_time)
+      return fail("pss_write_smf: bad note time");
+    // (a note shorter than a tick lasts one: its note-off sorts after its note-on)
+    if (t1 <= t0) t1 = t0 + 1;
+    ev.push_back({t0, 2, {0x90, (uint8_t)n.pitch, (uint8_t)n.velocity}});
+    ev.push_back({t1, 0, {0x80, (uint8_t)n.pitch, 0}});
+  }
+  for (auto& c : s->ccs) {
+    if (c.control_number < 0 || c.control_number > 127 || c.control_value < 0 || c.control_value > MAX_CC)
+      return fail("pss_write_smf: control change " + std::to_string(c.control_number) + " = " +
+                  std::to_string(c.control_value) + " outside 0..127");
+    int64_t t;
+    if (!to_tick(c.time, &t)) return fail("pss_write_smf: bad control change time");
+    ev.push_back({t, 1, {0xB0, (uint8_t)c.control_number, (uint8_t)c.control_value}});
+  }
+  std::stable_sort(ev.begin(), ev.end(),
+                   [](const Msg& a, const Msg& b) { return a.tick != b.tick ? a.tick < b.tick : a.rank < b.rank; });
+  int64_t end_tick = ev.empty() ? 0 : ev.back().tick, total;
+  if (!to_tick(s->total_time, &total)) return fail("pss_write_smf: bad total_time");
+  end_tick = std::max(end_tick, total);
+  if ((double)end_tick > MAX_TICK) return fail("pss_write_smf: the sequence is too long");
+  std::vector<uint8_t> trk;
+  auto varlen = [&](uint32_t v) {
+    uint8_t tmp[4];
+    int k = 0;
+    do { tmp[k++] = v & 0x7F; v >>= 7; } while (v);
+    while (k--) trk.push_back(tmp[k] | (k ? 0x80 : 0));
+  };
+  const uint8_t tempo[] = {0x00, 0xFF, 0x51, 0x03, (SMF_TEMPO >> 16) & 0xFF, (SMF_TEMPO >> 8) & 0xFF, SMF_TEMPO & 0xFF};
+  trk.insert(trk.end(), tempo, tempo + sizeof(tempo));
+  int64_t at = 0;
+  for (auto& e : ev) {
+    varlen((uint32_t)(e.tick - at));
+    at = e.tick;
+    trk.insert(trk.end(), e.b, e.b + 3);
+  }
+  varlen((uint32_t)(end_tick - at));
+  const uint8_t eot[] = {0xFF, 0x2F, 0x00};
+  trk.insert(trk.end(), eot, eot + sizeof(eot));
+  const size_t size = 14 + 8 + trk.size();
+  if (!out) return (int64_t)size;
+  if (capacity < size)
+    return fail("pss_write_smf: the file takes " + std::to_string(size) + " B, the buffer has " + std::to_string(capacity));
+  const uint32_t tl = (uint32_t)trk.size();
+  const uint8_t head[] = {'M', 'T', 'h', 'd', 0, 0, 0, 6, 0, 0, 0, 1, SMF_DIVISION >> 8, SMF_DIVISION & 0xFF,
+                          'M', 'T', 'r', 'k', (uint8_t)(tl >> 24), (uint8_t)(tl >> 16), (uint8_t)(tl >> 8), (uint8_t)tl};
+  memcpy(out, head, sizeof(head));
+  memcpy(out + sizeof(head), trk.data(), trk.size());
+  return (int64_t)size;
 }
 
 }  // extern "C"

@@ -537,6 +537,70 @@ class BatchedPianoEnv:
                                                             ("goal", "count", "keys", "fingers")), self.stream))
         return out
 
+    # -- the piano's sound module (models/piano/midi_module.py): what each env played
+    def record_midi(self, max_events: int = 2048, max_bytes: int = 0) -> None:
+        """Records every env's NoteOn / NoteOff / SustainOn / SustainOff messages on the device,
+        stamped with the physics substep they happened in (ps_record_midi). Two banks of
+        ``max_events`` per env, the running episode and the last finished one: 16 KB per env at
+        2048, 64 MB at 4096 envs. 0 turns recording off and frees them. Init-time: it
+        synchronises; not under graph capture."""
+        _lib.check(_lib.load().ps_record_midi(self._h, int(max_events), int(max_bytes)))
+        self.midi_max_events = int(max_events)
+
+    def _midi_which(self, which) -> int:
+        if which not in ("current", "previous"):
+            raise ValueError(f"which is 'current' or 'previous', not {which!r}")
+        return 1 if which == "previous" else 0
+
+    def midi_events(self, which: str = "current") -> Dict[str, Any]:
+        """The running (``"current"``) or last finished (``"previous"``) episode of every env
+        (ps_midi_events): ``events`` [N, max_events] int32 event words (music.decode_events; the
+        first ``count`` of an env are valid, the others 0), ``count``, ``dropped`` (events that did
+        not fit) and ``substeps`` (the episode's physics substeps so far) [N] int32."""
+        w = self._midi_which(which)
+        torch = self._torch
+        i = dict(device=self.device, dtype=torch.int32)
+        N = self.num_envs
+        out = dict(events=torch.empty(N, getattr(self, "midi_max_events", 0), **i), count=torch.empty(N, **i),
+                   dropped=torch.empty(N, **i), substeps=torch.empty(N, **i))
+        _lib.check(_lib.load().ps_midi_events(self._h, w, *(out[k].data_ptr() for k in
+                                                           ("events", "count", "dropped", "substeps")), self.stream))
+        return out
+
+    def midi_push(self, bits) -> None:
+        """``MidiModule.after_substep`` on caller-supplied activations (ps_midi_push): ``bits``
+        [N, rows, 3] event rows as music.pack_activations makes them, rows <= substeps per step."""
+        torch = self._torch
+        t = torch.as_tensor(bits, device=self.device).to(torch.int32).contiguous()
+        if t.dim() != 3 or t.shape[0] != self.num_envs or t.shape[2] != 3:
+            raise ValueError(f"bits must be [{self.num_envs}, rows, 3], got {tuple(t.shape)}")
+        _lib.check(_lib.load().ps_midi_push(self._h, t.data_ptr(), int(t.shape[1]), self.stream))
+        self._midi_bits = t  # keep alive until the kernel ran
+
+    def _midi_env(self, i: int, which: str):
+        # (an inspection call: it gathers every env's bank - [N, max_events] words, 32 MB at 4096
+        # envs and 2048 events - and synchronises the device to read one env's)
+        ev = self.midi_events(which)
+        self._torch.cuda.synchronize(self.device)
+        return (ev["events"][i].cpu().numpy(), int(ev["count"][i]), int(ev["dropped"][i]), int(ev["substeps"][i]))
+
+    def midi_messages(self, i: int, which: str = "current") -> list:
+        """Env ``i``'s messages (music.NoteOn / NoteOff / SustainOn / SustainOff) in the order the
+        reference's ``MidiModule.get_all_midi_messages`` has them; time in seconds of physics.
+        Not for the training loop: it copies all envs' banks and synchronises (``midi_events``
+        stays on the device)."""
+        words, count, _, _ = self._midi_env(i, which)
+        return music.decode_events(words, count, self.model_desc.timestep)
+
+    def performance(self, i: int, which: str = "current") -> music.NoteSequence:
+        """Env ``i``'s episode as a NoteSequence (music.sequence_from_messages): a note still on
+        at the episode's end (so far) is closed there; CC64 changes included; ``total_time`` the
+        episode's. ``music.write_midi`` makes a ``.mid`` file of it."""
+        words, count, _, substeps = self._midi_env(i, which)
+        dt = self.model_desc.timestep
+        return music.sequence_from_messages(music.decode_events(words, count, dt), substeps * dt,
+                                            title=f"env {i} ({which})")
+
     def obs_dict(self, obs=None) -> Dict[str, Any]:
         obs = self.obs if obs is None else obs
         return {k: obs[:, s] for k, s in self.obs_slices.items()}

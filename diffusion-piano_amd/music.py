@@ -23,6 +23,7 @@ Malformed input raises ``ValueError`` with the library's message.
 from __future__ import annotations
 
 import ctypes as C
+import enum
 import re
 from dataclasses import dataclass, field
 from pathlib import Path
@@ -38,6 +39,7 @@ NUM_KEYS = 88
 MAX_VELOCITY = 127
 SUSTAIN_PEDAL_CC_NUMBER = 64  # robopianist/music/constants.py:54
 MAX_CC_VALUE = 127
+SUSTAIN_ON_CC_VALUE = 64  # the value of the reference's SustainOn message (midi_message.py:82-90)
 
 # Maximum number of simultaneous notes per control step the device tables hold.
 MAX_NOTES_PER_STEP = 16
@@ -340,3 +342,165 @@ def test_midi(dt: float = 0.01) -> NoteSequence:
     seq.notes.append(Note(79, 2 * dt, 3 * dt, 80, 0))  # G5, right thumb.
     seq.total_time = 3 * dt
     return seq
+
+
+# ---------------------------------------------------------------------------------------
+# The piano's sound module: what an env played (models/piano/midi_module.py) -> messages ->
+# NoteSequence -> Standard MIDI File.
+# ---------------------------------------------------------------------------------------
+
+
+class EventType(enum.IntEnum):
+    """The kind field of a recorded event word (PS_MIDI_* of include/pianosim.h); the names are
+    those of ``robopianist/music/midi_message.py:25-32``."""
+    NOTE_ON = 0
+    NOTE_OFF = 1
+    SUSTAIN_ON = 2
+    SUSTAIN_OFF = 3
+
+
+@dataclass
+class NoteOn:
+    note: int
+    velocity: int
+    time: float
+    event_type = EventType.NOTE_ON
+
+
+@dataclass
+class NoteOff:
+    note: int
+    time: float
+    event_type = EventType.NOTE_OFF
+
+
+@dataclass
+class SustainOn:
+    """CC64 with the reference's value for "on", 64 (midi_message.py:82-90)."""
+    time: float
+    control: int = SUSTAIN_PEDAL_CC_NUMBER
+    value: int = SUSTAIN_ON_CC_VALUE
+    event_type = EventType.SUSTAIN_ON
+
+
+@dataclass
+class SustainOff:
+    time: float
+    control: int = SUSTAIN_PEDAL_CC_NUMBER
+    value: int = 0
+    event_type = EventType.SUSTAIN_OFF
+
+
+EVENT_NOTE_BITS, EVENT_KIND_BITS = 8, 2  # then the substep ordinal, 22 bits
+EVENT_ORDINAL_SHIFT = EVENT_NOTE_BITS + EVENT_KIND_BITS
+EVENT_ORDINAL_MAX = (1 << 22) - 1
+
+
+def encode_event(note: int, kind: int, ordinal: int) -> int:
+    """The recorder's event word: note number | kind << 8 | substep ordinal << 10."""
+    if not (0 <= note < 1 << EVENT_NOTE_BITS and 0 <= kind < 1 << EVENT_KIND_BITS and 0 <= ordinal <= EVENT_ORDINAL_MAX):
+        raise ValueError(f"event field out of range: note {note}, kind {kind}, ordinal {ordinal}")
+    return note | kind << EVENT_NOTE_BITS | ordinal << EVENT_ORDINAL_SHIFT
+
+
+def event_fields(words) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """-> (note, kind, ordinal) arrays of event words (any integer dtype; int32 words are taken
+    as the uint32 they hold)."""
+    w = np.asarray(words)
+    w = w.view(np.uint32) if w.dtype == np.int32 else w.astype(np.uint32)
+    return ((w & 0xFF).astype(np.int64), ((w >> EVENT_NOTE_BITS) & 3).astype(np.int64),
+            (w >> EVENT_ORDINAL_SHIFT).astype(np.int64))
+
+
+def _message(note: int, kind: int, time: float):
+    if kind == EventType.NOTE_ON:
+        return NoteOn(note, MAX_VELOCITY, time)  # the reference's constant (midi_module.py:67-69)
+    if kind == EventType.NOTE_OFF:
+        return NoteOff(note, time)
+    return SustainOn(time) if kind == EventType.SUSTAIN_ON else SustainOff(time)
+
+
+def decode_events(words, count: int, timestep: float) -> list:
+    """The first ``count`` event words as messages; time = ordinal * timestep."""
+    note, kind, ordinal = event_fields(np.asarray(words)[:int(count)])
+    return [_message(int(n), int(k), int(o) * timestep) for n, k, o in zip(note, kind, ordinal)]
+
+
+def events_from_activations(act, sustain, timestep: float, words: bool = False):
+    """``MidiModule.after_substep`` (models/piano/midi_module.py:47-98) over a whole episode:
+    ``act`` [S, 88] bool and ``sustain`` [S] bool are the activations after substeps 1 .. S, all
+    off before the first. Per substep: the NoteOns by ascending key, the NoteOffs by ascending
+    key, SustainOn, SustainOff, each stamped ``ordinal * timestep``. ``words``: the event words
+    (uint32 array) instead of messages. This is the specification of the device recorder."""
+    act = np.asarray(act, dtype=bool).reshape(-1, NUM_KEYS)
+    sustain = np.asarray(sustain, dtype=bool).reshape(-1)
+    if len(sustain) != len(act):
+        raise ValueError("act and sustain differ in length")
+    prev, prev_s = np.zeros(NUM_KEYS, bool), False
+    out = []
+    for s in range(len(act)):
+        o = s + 1
+        changed = act[s] ^ prev
+        out += [(MIN_MIDI_PITCH_PIANO + int(k), EventType.NOTE_ON, o) for k in np.flatnonzero(changed & act[s])]
+        out += [(MIN_MIDI_PITCH_PIANO + int(k), EventType.NOTE_OFF, o) for k in np.flatnonzero(changed & ~act[s])]
+        if bool(sustain[s]) != prev_s:
+            out.append((0, EventType.SUSTAIN_ON if sustain[s] else EventType.SUSTAIN_OFF, o))
+        prev, prev_s = act[s].copy(), bool(sustain[s])
+    if words:
+        return np.array([encode_event(n, int(k), min(o, EVENT_ORDINAL_MAX)) for n, k, o in out], np.uint32)
+    return [_message(n, k, o * timestep) for n, k, o in out]
+
+
+def pack_activations(act, sustain) -> np.ndarray:
+    """[S, 88] bool, [S] bool -> [S, 3] uint32 rows as ``ps_midi_push`` takes them: key k is bit
+    k % 32 of word k // 32, the sustain activation bit 24 of word 2."""
+    act = np.asarray(act, dtype=bool).reshape(-1, NUM_KEYS)
+    bits = np.zeros((len(act), 96), bool)
+    bits[:, :NUM_KEYS] = act
+    bits[:, NUM_KEYS] = np.asarray(sustain, dtype=bool).reshape(-1)
+    weights = (1 << np.arange(32, dtype=np.uint64))
+    return (bits.reshape(len(act), 3, 32).astype(np.uint64) * weights).sum(-1).astype(np.uint32)
+
+
+def sequence_from_messages(messages, end_time: float, title: str = "") -> NoteSequence:
+    """Messages in time order -> a NoteSequence: a NoteOn opens its pitch (velocity as recorded),
+    the next NoteOff of the pitch closes it, a note still on at the end is closed at
+    ``end_time``; the pedal messages become CC64 control changes with their values (64 / 0).
+    Notes in order of their starts; ``total_time`` = ``end_time``."""
+    seq = NoteSequence(title=title, total_time=float(end_time))
+    open_notes = {}
+    order = []
+    for m in messages:
+        if m.event_type == EventType.NOTE_ON:
+            if m.note in open_notes:  # (a re-strike without a NoteOff: the sounding note ends here)
+                open_notes.pop(m.note).end_time = m.time
+            n = Note(m.note, m.time, float(end_time), m.velocity, 0)
+            open_notes[m.note] = n
+            order.append(n)
+        elif m.event_type == EventType.NOTE_OFF:
+            if m.note in open_notes:
+                open_notes.pop(m.note).end_time = m.time
+        else:
+            seq.control_changes.append(ControlChange(m.time, m.control, m.value))
+    seq.notes = order
+    return seq
+
+
+def to_smf(seq: NoteSequence) -> bytes:
+    """The sequence as a Standard MIDI File (``pss_write_smf``): format 0, 1000 ticks per quarter
+    note at 120 qpm = 2000 ticks per second, so times on the 5 ms physics grid are exact.
+    Raises ValueError on a pitch, velocity or controller value outside 0..127."""
+    L = _lib.load_song()
+    s = _Seq.of(seq)
+    size = L.pss_write_smf(s.h, None, 0)
+    if size < 0:
+        _check(-1)
+    buf = (C.c_uint8 * size)()
+    if L.pss_write_smf(s.h, buf, size) != size:
+        _check(-1)
+    return bytes(buf)
+
+
+def write_midi(seq: NoteSequence, path) -> None:
+    """``MidiFile.save`` (midi_file.py:191-195): ``to_smf(seq)`` into ``path``."""
+    Path(path).write_bytes(to_smf(seq))

@@ -464,6 +464,49 @@ int ps_set_augmentation(ps_env* env, const int32_t* song, const double* factor, 
 int ps_get_song_tables(ps_env* env, float* goal, int32_t* count, int32_t* keys, int32_t* fingers,
                        void* stream);
 
+/* ---- the piano's sound module on the device (robopianist/models/piano/midi_module.py, driven
+ * after every physics substep from piano.py:154-162): every env's NoteOn / NoteOff / SustainOn /
+ * SustainOff messages, stamped with the substep they happened in. A recording handle's step
+ * kernel keeps the key and sustain activations at the end of every substep, and a second kernel
+ * that ps_step and ps_reset enqueue after it appends what changed to the env's running episode:
+ * no host sync, legal under stream capture. Inside one substep the order is the reference's:
+ * NoteOns by ascending key, NoteOffs by ascending key, SustainOn, SustainOff.
+ *
+ * An event is one uint32: bits 0-7 the MIDI note number (key + 21; 0 for the pedal), bits 8-9
+ * the kind (PS_MIDI_*), bits 10-31 the substep's ordinal in the episode, the first substep
+ * being 1. Its time is ordinal * timestep: physics.data.time after that substep. The velocity is
+ * the reference's constant 127. After a physics warning (PS_WARN_*) MuJoCo's time restarts at 0;
+ * the ordinal goes on, and the keys' jump to 0 gives their NoteOffs.
+ *
+ * Per env two banks of max_events events: the running episode and the last finished one (a
+ * reset, ps_reset's or the auto-reset after LAST, swaps them), so a finished performance stays
+ * readable for the whole next episode. An event that does not fit is counted in `dropped` and
+ * not written. */
+#define PS_MIDI_NOTE_ON 0
+#define PS_MIDI_NOTE_OFF 1
+#define PS_MIDI_SUSTAIN_ON 2
+#define PS_MIDI_SUSTAIN_OFF 3
+#define PS_MIDI_ORDINAL_SHIFT 10
+#define PS_MIDI_ORDINAL_MAX ((1u << 22) - 1) /* later substeps keep this ordinal */
+/* Init-time (it allocates and synchronises; not under stream capture): turns recording on with
+ * banks of max_events events, or off (max_events 0), freeing the buffers. Recording starts with
+ * all keys and the pedal taken as off. n_envs * (8 * max_events + 4 * (1 + 3 * n_substeps) + 40)
+ * bytes; fails, with the sizes in the message, when that exceeds max_bytes (0: no limit) - the
+ * handle is then left as it was, recording or not. Every other call replaces the banks: what
+ * was recorded before it is gone. */
+int ps_record_midi(ps_env* env, int max_events, uint64_t max_bytes);
+/* Bank `which` (0: the running episode, 1: the last finished one) of every env: events
+ * [N][max_events] (the first count[i] of env i are valid), count / dropped [N], substeps [N] (the
+ * episode's physics substeps so far: its length is substeps * timestep). Device pointers; any
+ * may be NULL. */
+int ps_midi_events(ps_env* env, int which, uint32_t* events, int32_t* count, int32_t* dropped,
+                   int32_t* substeps, void* stream);
+/* MidiModule.after_substep as an entry point: appends the messages of caller-supplied activation
+ * rows bits [N][rows][3] (device) to every env's running episode, as if a step had produced them:
+ * key k is bit k % 32 of word k / 32, the sustain activation bit 24 of word 2; 1 <= rows <= the
+ * handle's n_substeps. */
+int ps_midi_push(ps_env* env, const uint32_t* bits, int rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,18 @@ int pss_build_tables(const pss_flat_song* song, double factor, int shift, double
 int pss_draw_augmentation(uint64_t seed, uint32_t env, uint32_t episode, const pss_variation* vars, int n_vars,
                           const pss_flat_song* bank, int n_songs, int* song, double* factor, int* shift);
 
+/* The sequence as a Standard MIDI File (the reference exports through note_seq's
+ * note_sequence_to_midi_file, midi_file.py:186-188): format 0, one track, 1000 ticks per quarter
+ * note and one tempo event of 500000 us per quarter note, i.e. 2000 ticks per second - a time on
+ * the 5 ms physics grid is a whole number of ticks. Times are rounded to the nearest tick; events
+ * are sorted by tick, at one tick note-offs before control changes before note-ons (a re-strike
+ * of a pitch at the tick its previous note ends reads back as two notes); a note shorter than
+ * a tick lasts one; channel 0; control values as given. Returns the file's size in bytes and,
+ * when out is not NULL, writes it (capacity must be at least the size). < 0: a pitch, velocity,
+ * controller number or value outside 0..127, a negative or non-finite time (total_time
+ * included), a buffer too small. */
+int64_t pss_write_smf(const pss_seq* seq, uint8_t* out, size_t capacity);
+
 #ifdef __cplusplus
 }
 #endif
