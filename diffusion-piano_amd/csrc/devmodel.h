@@ -36,6 +36,7 @@ constexpr int YKEY = 19;
 constexpr int NTRI = MAXDEP * (MAXDEP - 1) / 2;  // (a,b) pairs 1<=a<=b<=8
 constexpr int NKB = 64;        // key-range buckets along y
 constexpr int KGEO = 16;       // floats per key collision record
+constexpr int MAXFORE = 64;    // root-body pairs of the forearm prefilter (one per lane)
 // hull support cells: the direction sphere as a cube map of 6 faces x XCG x XCG cells; per hull
 // and cell the vertices that can be the support of a direction in the cell (DevModel::x_cell)
 constexpr int XCG = 4;
@@ -92,9 +93,9 @@ struct DevModel {
   // fingertip sites
   int site_body[NH * PS_NFINGER];
   float site_pos[NH * PS_NFINGER][3];
-  // capsule-capsule pairs
+  // capsule-capsule pairs: a | b << 8 (as xpair: nothing to combine at the load)
   int npairs;
-  int pair[PS_MAX_CAPPAIRS][2];
+  uint16_t pair[PS_MAX_CAPPAIRS];
   // extra (box / hull) colliders, global extra index e = h*NX + i (lane NGT + e)
   int nx;                      // extra colliders in use (0: the extra passes are skipped)
   int x_type[NXT];             // PS_GEOM_NONE / BOX / HULL
@@ -132,6 +133,11 @@ struct DevModel {
   // per-key collision record, staged into LDS by collide2: pos(3) half(3) anchor(3), then the
   // conservative AABB of the key box over its joint range: xlo xhi ylo yhi ztop, pad
   alignas(16) float key_geo[NK][KGEO];
+  // the forearm term's prefilter (kernel_v2.inc, fore_near): the capsule and extra pairs whose two
+  // colliders sit on the two hands' root bodies, a | b << 8 - the only pairs whose contact the
+  // forearm term counts. nfore = -1: more than MAXFORE of them (no prefilter)
+  int nfore;
+  uint16_t fore_pair[MAXFORE];
 };
 
 }  // namespace ps

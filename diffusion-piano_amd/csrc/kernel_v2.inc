@@ -13,6 +13,7 @@
 
 #ifdef PS_TIMING
 #define NPHASE 56
+enum : int { TS_FINAL = 52, TS_FINAL_SKIP = 53 };  // counters: env-steps, and those without the final collide pass
 #define TARG , uint64_t *tacc, uint64_t &tlast
 #define TPASS , tacc, tlast
 #define TSTAMP(slot)                                     \
@@ -504,6 +505,10 @@ __device__ __forceinline__ int collide2(const DevModel* __restrict__ m, Shared& 
     S.kb[0][lane] = m->kb_first[lane];
     S.kb[1][lane] = m->kb_end[lane];
   }
+  // lane NGT + e: the type and bounding radius of box / hull collider e, fetched once per pass with
+  // the staging above (the hand boxes, the collider lanes and the hand-hand spheres read them here)
+  const int x_ty = XG ? m->x_type[lane >= NGT ? lane - NGT : 0] : (int)PS_GEOM_NONE;
+  const float x_rbl = XG ? m->x_rb[lane >= NGT ? lane - NGT : 0] : 0.f;
   wsync();
   // piano: the (capsule, key|base) candidate pairs of all capsules, compacted in canonical
   // order into the (dead between dynamics and the next kinematics) body exchange buffer,
@@ -565,11 +570,11 @@ __device__ __forceinline__ int collide2(const DevModel* __restrict__ m, Shared& 
   int hb = lane < NG ? 0 : 1;
   if (XG && lane >= NGT) {
     const int e = lane - NGT;
-    inb = m->x_type[e] != PS_GEOM_NONE;
+    inb = x_ty != PS_GEOM_NONE;
     hb = e / NX;
     if (inb) {
       const f3 ctr = ld3(S.xg[e]);
-      const float rb = m->x_rb[e];
+      const float rb = x_rbl;
       lo[0] = ctr.x - rb; lo[1] = ctr.y - rb; lo[2] = ctr.z - rb;
       hi[0] = ctr.x + rb; hi[1] = ctr.y + rb; hi[2] = ctr.z + rb;
     }
@@ -589,21 +594,29 @@ __device__ __forceinline__ int collide2(const DevModel* __restrict__ m, Shared& 
   // into the candidate buffer; pass 2: segment-segment distance on the survivors only
   uint16_t* near = cand;
   int nnear = 0;
-  int pnext = lane < npairs ? m->pair[lane][0] | (m->pair[lane][1] << 8) : 0;
-  for (int p0 = 0; p0 < npairs; p0 += 64) {
-    const int p = p0 + lane;
-    const int pk = pnext;
-    if (p0 + 64 < npairs) pnext = p + 64 < npairs ? m->pair[p + 64][0] | (m->pair[p + 64][1] << 8) : 0;
-    bool pass = false;
-    if (p < npairs) {
-      const float* A = S.cap[pk & 255];
-      const float* B = S.cap[pk >> 8];
-      const f3 ca = (ld3(A) + ld3(A + 3)) * 0.5f, cb = (ld3(B) + ld3(B + 3)) * 0.5f;
-      pass = norm3(ca - cb) <= A[7] + B[7] + A[6] + B[6];
+  // (PTRIPS trips' table entries are loaded together, lanes past the list with their index clamped
+  // into it, and consumed after one round trip; the survivors are compacted trip by trip, in pair
+  // order)
+  constexpr int PTRIPS = 4;
+  for (int p0 = 0; p0 < npairs; p0 += 64 * PTRIPS) {
+    int pks[PTRIPS];
+#pragma unroll
+    for (int u = 0; u < PTRIPS; u++) pks[u] = m->pair[min(p0 + 64 * u + lane, npairs - 1)];
+#pragma unroll
+    for (int u = 0; u < PTRIPS; u++) {
+      const int p = p0 + 64 * u + lane;
+      const int pk = pks[u];
+      bool pass = false;
+      if (p < npairs) {
+        const float* A = S.cap[pk & 255];
+        const float* B = S.cap[pk >> 8];
+        const f3 ca = (ld3(A) + ld3(A + 3)) * 0.5f, cb = (ld3(B) + ld3(B + 3)) * 0.5f;
+        pass = norm3(ca - cb) <= A[7] + B[7] + A[6] + B[6];
+      }
+      const uint64_t mask = __ballot(pass);
+      if (pass) near[nnear + lanes_below(mask, lane)] = (uint16_t)pk;
+      nnear += __popcll(mask);
     }
-    const uint64_t mask = __ballot(pass);
-    if (pass) near[nnear + lanes_below(mask, lane)] = (uint16_t)pk;
-    nnear += __popcll(mask);
   }
   wsync();
   for (int q0 = 0; q0 < nnear && base < maxc; q0 += 64) {
@@ -653,7 +666,7 @@ __device__ __forceinline__ int collide2(const DevModel* __restrict__ m, Shared& 
       // its own slots (past the longest list without overflow: NXT * CPL < CSTAGE_OFF / 2), copied
       // to their compacted places after the scan; a second pass only on overflow
       static_assert(NXT * CPL * 2 <= CSTAGE_OFF, "x candidates overlap the staging");
-      const bool isx = lane >= NGT && m->x_type[lane >= NGT ? lane - NGT : 0] != PS_GEOM_NONE;
+      const bool isx = lane >= NGT && x_ty != PS_GEOM_NONE;
       uint16_t* cst = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(&S.bx[0][0]) + CSTAGE_OFF) + lane * CPL;
       wsync();  // (the capsule pairs' list has been read)
       const int cnt = isx ? xpiano_candidates(m, S, lane, cst, CPL) : 0;
@@ -670,32 +683,39 @@ __device__ __forceinline__ int collide2(const DevModel* __restrict__ m, Shared& 
     TSTAMP(32);
     if (m->nxpairs) {  // hand-hand: bounding spheres
       const int nxp = apart ? m->nxpairs_same : m->nxpairs;  // cross-hand ones: only when the boxes meet
-      for (int p0 = 0; p0 < nxp; p0 += 64) {
-        const int p = p0 + lane;
-        bool pass = false;
-        int pk = 0;
-        if (p < nxp) {
-          pk = m->xpair[p];
-          const int ga = pk & 255, gb = pk >> 8;
-          f3 c2[2];
-          float rad = 0.f;
+      for (int p0 = 0; p0 < nxp; p0 += 64 * PTRIPS) {  // (entries of PTRIPS trips per round trip, as above)
+        int pks[PTRIPS];
 #pragma unroll
-          for (int q = 0; q < 2; q++) {
-            const int g = q ? gb : ga;
-            if (g < NGT) {
-              c2[q] = (ld3(&S.cap[g][0]) + ld3(&S.cap[g][3])) * 0.5f;
-              rad += S.cap[g][6] + S.cap[g][7];
-            } else {
-              c2[q] = ld3(S.xg[g - NGT]);
-              rad += m->x_rb[g - NGT];
+        for (int u = 0; u < PTRIPS; u++) pks[u] = m->xpair[min(p0 + 64 * u + lane, nxp - 1)];
+#pragma unroll
+        for (int u = 0; u < PTRIPS; u++) {
+          const int p = p0 + 64 * u + lane;
+          const int pk = pks[u];
+          const int ga = pk & 255, gb = pk >> 8;
+          // (the bounding radii from the collider lanes: an exchange of the whole wave)
+          const float rba = __shfl(x_rbl, ga, 64), rbb = __shfl(x_rbl, gb, 64);
+          bool pass = false;
+          if (p < nxp) {
+            f3 c2[2];
+            float rad = 0.f;
+#pragma unroll
+            for (int q = 0; q < 2; q++) {
+              const int g = q ? gb : ga;
+              if (g < NGT) {
+                c2[q] = (ld3(&S.cap[g][0]) + ld3(&S.cap[g][3])) * 0.5f;
+                rad += S.cap[g][6] + S.cap[g][7];
+              } else {
+                c2[q] = ld3(S.xg[g - NGT]);
+                rad += q ? rbb : rba;
+              }
             }
+            pass = norm3(c2[0] - c2[1]) <= rad;
           }
-          pass = norm3(c2[0] - c2[1]) <= rad;
+          const uint64_t mask = __ballot(pass);
+          const int at = nl + lanes_below(mask, lane);
+          if (pass && at < MAXCAND) cand[at] = (uint16_t)(pk | XHH);
+          nl = min(nl + __popcll(mask), MAXCAND);
         }
-        const uint64_t mask = __ballot(pass);
-        const int at = nl + lanes_below(mask, lane);
-        if (pass && at < MAXCAND) cand[at] = (uint16_t)(pk | XHH);
-        nl = min(nl + __popcll(mask), MAXCAND);
       }
 #ifdef PS_TIMING
       tacc[45] += nl;  // (hand-hand pairs past the bounding spheres + piano candidates)
@@ -730,6 +750,57 @@ __device__ __forceinline__ int collide2(const DevModel* __restrict__ m, Shared& 
   if (lane == 0) S.ncon = base < maxc ? base : maxc;
   wsync();
   return base;
+}
+
+// The forearm term's prefilter, after kinematics2 of the state: can any pair of colliders on the
+// two hands' root bodies (DevModel::fore_pair, one per lane) touch? A contact of such a pair is
+// all the forearm term looks for. Two capsules: collide2 reports a contact when the points seg_seg
+// finds on the two segments are at most ra + rb apart, and no two points of the segments are
+// closer than the gap between the segments' bounding boxes - so none when that gap exceeds
+// ra + rb by the margin (0.1 mm: five orders above the rounding of either side). A pair with a
+// box / hull collider: collide2 tests its shapes only past the bounding spheres, the test repeated
+// here with a margin for the rounding of the sums. When no pair passes, no contact list - capped
+// or not - holds a forearm hit. Wave-uniform.
+template <bool XG>
+__device__ __forceinline__ bool fore_near(const DevModel* __restrict__ m, const Shared& S, int lane) {
+  const int nf = m->nfore;
+  if (nf < 0) return true;  // (too many pairs for one trip: no prefilter)
+  bool pass = false;
+  if (lane < nf) {
+    const int pk = m->fore_pair[lane];
+    const int ga = pk & 255, gb = pk >> 8;
+    if (ga < NGT && gb < NGT) {
+      const float *A = S.cap[ga], *B = S.cap[gb];
+      const float reach = A[6] + B[6] + 1e-4f;
+      float d2 = 0.f;
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        const float alo = fminf(A[i], A[3 + i]), ahi = fmaxf(A[i], A[3 + i]);
+        const float blo = fminf(B[i], B[3 + i]), bhi = fmaxf(B[i], B[3 + i]);
+        const float gap = fmaxf(0.f, fmaxf(alo - bhi, blo - ahi));
+        d2 += gap * gap;
+      }
+      pass = !(d2 > reach * reach);
+    } else if (XG) {
+      f3 c2[2];
+      float rad = 0.f;
+#pragma unroll
+      for (int q = 0; q < 2; q++) {
+        const int g = q ? gb : ga;
+        if (g < NGT) {
+          c2[q] = (ld3(&S.cap[g][0]) + ld3(&S.cap[g][3])) * 0.5f;
+          rad += S.cap[g][6] + S.cap[g][7];
+        } else {
+          c2[q] = ld3(S.xg[min(g - NGT, NXT - 1)]);
+          rad += m->x_rb[min(g - NGT, NXT - 1)];
+        }
+      }
+      pass = !(norm3(c2[0] - c2[1]) > rad * 1.00001f + 1e-6f);
+    } else {
+      pass = true;  // (a box / hull pair in the capsule-only kernel: never skipped)
+    }
+  }
+  return __ballot(pass) != 0ull;
 }
 
 // ------------------------------------------------------------------ per-lane state
@@ -1778,7 +1849,15 @@ __device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__
   }
   // ---- mj_step1 at the final state + task layer
   kinematics2<false, XG>(m, S, L, D, lane, hand_dy TPASS);
-  collide2<XG, WPE>(m, S, cfg.maxcon, lane, L.c_r TPASS);
+  // The final state's contact list has three readers: the forearm term, ps_contact_count and
+  // ps_contacts. The pass runs when contacts are recorded (con_out) or the forearm term could find
+  // its contact (fore_near); otherwise it is skipped and bufs.ncon[e] is left as it was: the host
+  // knows the counts are stale and materialises them when asked (pianosim_ncon_kernel).
+  const bool final_con = bufs.con_out != nullptr || (!do_reset && cfg.forearm && fore_near<XG>(m, S, lane));
+  if (final_con) collide2<XG, WPE>(m, S, cfg.maxcon, lane, L.c_r TPASS);
+#ifdef PS_TIMING
+  if (lane == 0 && !do_reset) { tacc[TS_FINAL] += 1; tacc[TS_FINAL_SKIP] += !final_con; }
+#endif
   key_state2(m, S, D, lane);
   // the one-hand task's <rh|lh>_shadow_hand/position: the kept hand's root body (hands/base.py:
   // 112-114); its lane is the body's (as site_world2)
@@ -1811,7 +1890,7 @@ __device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__
       bufs.sustain[e] = 0.f;
       bufs.t_idx[e] = 0;
       bufs.last[e] = 0;
-      bufs.ncon[e] = S.ncon;
+      if (final_con) bufs.ncon[e] = S.ncon;
       if (bufs.keybits) bufs.keybits[(size_t)e * kb_stride(m->nsub)] = KB_NEW_EPISODE;
       if (mode == 0) {
         reward[e] = 0.f;
@@ -1926,7 +2005,7 @@ __device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__
   float fore = 0.f;
   if (cfg.forearm) {
     bool hit = false;
-    if (lane < S.ncon) {
+    if (final_con && lane < S.ncon) {  // (no pass: fore_near found no root-body pair near)
       const Contact& cc = S.con[lane];
       if (cc.kind == 2) {
         // rh root-body geom against lh root-body geom (piano_with_shadow_hands.py:251-259)
@@ -1981,7 +2060,7 @@ __device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__
     bufs.sustain[e] = S.sustain;
     bufs.t_idx[e] = t_new;
     bufs.last[e] = terminal ? 1 : 0;
-    bufs.ncon[e] = S.ncon;
+    if (final_con) bufs.ncon[e] = S.ncon;
     if (bufs.keybits) bufs.keybits[(size_t)e * kb_stride(m->nsub)] = (uint32_t)m->nsub;
   }
   if (bufs.con_out) {  // inspection copy of the contact list (ps_contacts)
@@ -2015,6 +2094,39 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) 
   const int lane = threadIdx.x;
   if (e >= n_envs) return;
   env_step<XG, WPE, false>(S, m, song, cfg, bufs, action, mask, obs, reward, discount, step_type, mode, e, lane, 0, 1);
+}
+
+// The contact counts of the envs' current state rows, on demand (ps_contact_count after steps or
+// resets that skipped the final-state pass): the rows hold the lane state env_step's final
+// kinematics2 + collide2 had, so this is that pass, and bufs.ncon[e] the count it would have
+// written. One workgroup per env.
+template <bool XG>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PS_WAVES_PER_EU))) pianosim_ncon_kernel(
+    const DevModel* __restrict__ m, Cfg cfg, Bufs bufs, int n_envs) {
+  __shared__ Shared S;
+  const int e = blockIdx.x, lane = threadIdx.x;
+  if (e >= n_envs) return;
+#ifdef PS_TIMING
+  uint64_t tacc[NPHASE] = {0};
+  uint64_t tlast = 0;
+#endif
+  LaneStatic L;
+  load_static(m, S, L, lane);
+  LaneDyn D;
+  const size_t rowoff = (size_t)e * NV;
+  D.v = 0.f;
+  D.q = bufs.qpos[rowoff + NK + (lane < NDT ? lane : 0)];
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    const int k = lane + 64 * j;
+    D.kq[j] = bufs.qpos[rowoff + (k < NK ? k : 0)];
+    D.kv[j] = 0.f;
+  }
+  const float hand_dy = cfg.randomize ? bufs.hand_dy[e] : 0.f;
+  wsync();
+  kinematics2<false, XG>(m, S, L, D, lane, hand_dy TPASS);
+  collide2<XG, PS_WAVES_PER_EU>(m, S, cfg.maxcon, lane, L.c_r TPASS);
+  if (lane == 0) bufs.ncon[e] = S.ncon;
 }
 
 enum : int { QC_HEAD = 0, QC_WORDS = 32 };  // (the ticket counter on a line of its own)

@@ -501,19 +501,18 @@ inline int build_dev_model(const ps_model_desc* d, DevModel* m, int hand_side, s
   if (d->n_cappairs < 0 || d->n_cappairs > PS_MAX_CAPPAIRS) return refuse(err, "bad n_cappairs");
   m->npairs = d->n_cappairs;
   for (int i = 0; i < d->n_cappairs; i++) {
-    m->pair[i][0] = d->cappair[i][0];
-    m->pair[i][1] = d->cappair[i][1];
-    if (m->pair[i][0] < 0 || m->pair[i][0] >= NGT || m->pair[i][1] < 0 || m->pair[i][1] >= NGT)
-      return refuse(err, "capsule pair index out of range");
-    if (m->geom_r[m->pair[i][0]] < 0.f || m->geom_r[m->pair[i][1]] < 0.f) return refuse(err, "capsule pair names an unused slot");
+    const int a = d->cappair[i][0], b = d->cappair[i][1];
+    if (a < 0 || a >= NGT || b < 0 || b >= NGT) return refuse(err, "capsule pair index out of range");
+    if (m->geom_r[a] < 0.f || m->geom_r[b] < 0.f) return refuse(err, "capsule pair names an unused slot");
+    m->pair[i] = (uint16_t)(a | (b << 8));
   }
   // the cross-hand pairs can be skipped wholesale when the hands' boxes are apart, if they
   // all come after the same-hand ones (model.capsule_pairs orders them so)
+  auto same_hand = [m](int i) { return (m->pair[i] & 255) / NG == (m->pair[i] >> 8) / NG; };
   m->npairs_same = 0;
-  while (m->npairs_same < m->npairs && m->pair[m->npairs_same][0] / NG == m->pair[m->npairs_same][1] / NG)
-    m->npairs_same++;
+  while (m->npairs_same < m->npairs && same_hand(m->npairs_same)) m->npairs_same++;
   for (int i = m->npairs_same; i < m->npairs; i++)
-    if (m->pair[i][0] / NG == m->pair[i][1] / NG) { m->npairs_same = m->npairs; break; }
+    if (same_hand(i)) { m->npairs_same = m->npairs; break; }
   // likewise the pairs with an extra collider (model.extra_pairs: same-hand ones first)
   auto xhand = [](int g) { return g < NGT ? g / NG : (g - NGT) / NX; };
   m->nxpairs_same = 0;
@@ -522,6 +521,17 @@ inline int build_dev_model(const ps_model_desc* d, DevModel* m, int hand_side, s
     m->nxpairs_same++;
   for (int i = m->nxpairs_same; i < m->nxpairs; i++)
     if (xhand(m->xpair[i] & 255) == xhand(m->xpair[i] >> 8)) { m->nxpairs_same = m->nxpairs; break; }
+  // the forearm term counts a hand-hand contact whose two colliders sit on the two hands' root
+  // bodies (env_step's rule, restated on the pairs): only these pairs can produce one
+  m->nfore = 0;
+  auto fore = [m](int a, int b) {
+    const int ba = m->geom_body[a], bb = m->geom_body[b];
+    if (ba % NB != 0 || bb % NB != 0 || ba == bb || m->nfore < 0) return;
+    if (m->nfore == MAXFORE) { m->nfore = -1; return; }
+    m->fore_pair[m->nfore++] = (uint16_t)(a | (b << 8));
+  };
+  for (int i = 0; i < m->npairs; i++) fore(m->pair[i] & 255, m->pair[i] >> 8);
+  for (int i = 0; i < m->nxpairs; i++) fore(m->xpair[i] & 255, m->xpair[i] >> 8);
   return 0;
 }
 

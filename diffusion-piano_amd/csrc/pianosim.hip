@@ -102,6 +102,11 @@ struct ps_env {
   int* qrank;               // [n] env -> its position in order_kernel's order of this step
   uint64_t* qtrace;         // -DPS_QTRACE: [n * chunks][QT_ITEM] + [grid][QT_EXIT] (ps_debug_qtrace)
   Contact* con_out;         // [N][MAXCON] contact lists of the last step (ps_record_contacts)
+  // ncon is lazy: a step or reset launch without contact recording may skip the final-state
+  // collision pass (env_step) and then leaves its envs' counts unwritten. ncon_stale: set by such
+  // a launch, cleared by materialise_ncon (the pass alone, from the state rows). ncon_sticky: such
+  // a launch was captured into a graph - replays set no flag, so the counts stay stale for good
+  bool ncon_stale, ncon_sticky;
   // per-episode MIDI augmentations (ps_set_augmentations): the device bank and per-env tables,
   // the builder's dynamic LDS bytes
   bool aug_on;
@@ -344,13 +349,8 @@ __global__ void __launch_bounds__(ORDER_THREADS) order_kernel(const int* __restr
   }
 }
 
-static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask, float* obs, float* reward,
-                  float* discount, uint8_t* step_type, void* stream) {
-  Song song{E->T, E->d_goal, E->d_count, E->d_keys, E->d_fingers, 0, nullptr};
-  if (E->aug_on) {
-    song = Song{E->T, E->aug.goal, E->aug.count, E->aug.keys, E->aug.fingers, E->aug.T_cap, E->aug.T};
-    if (launch_builder(E, mode == 1 ? AUG_RESET : AUG_STEP, mask, nullptr, nullptr, nullptr, stream)) return -1;
-  }
+// the kernels' view of the handle: its task options and its buffers
+static Cfg make_cfg(const ps_env* E) {
   // (the one-hand task has no forearm term: forearm_reward is ignored)
   Cfg cfg{};
   cfg.lookahead = E->cfg.n_steps_lookahead;
@@ -368,6 +368,10 @@ static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask,
   cfg.full_cpl = E->full_cpl;
   cfg.refine = E->cfg.solver_refine;
   cfg.hand = E->cfg.hand_side;
+  return cfg;
+}
+
+static Bufs make_bufs(const ps_env* E) {
   Bufs b{};  // (the handle's buffer of the same name, but `applied`)
   b.qpos = E->qpos; b.qvel = E->qvel; b.qws = E->qws; b.ctrl = E->ctrl; b.sustain = E->sustain;
   b.t_idx = E->t_idx; b.last = E->last; b.terms = E->terms; b.tips = E->tips; b.ncon = E->ncon;
@@ -375,6 +379,58 @@ static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask,
   b.episode = E->episode; b.stats = E->stats; b.con_out = E->con_out; b.warnings = E->warnings; b.park = E->park;
   b.applied = E->applied_on ? E->applied : nullptr;
   b.keybits = E->keybits;
+  return b;
+}
+
+// is work put on the stream being captured into a graph (it runs at the graph's replays, not now)?
+static bool capturing(void* stream) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return cs != hipStreamCaptureStatusNone;
+}
+
+// bufs.ncon of the envs' current state rows (pianosim_ncon_kernel), if a launch since the last
+// call may have left it unwritten. Called before the counts are read and before anything but a
+// step or reset launch overwrites the state rows or hand_dy: the counts stay those of the last
+// launch's final state. Under graph capture the pass is always put on the stream - the graph's
+// replays cannot know what ran before them - and clears nothing: it has not run.
+static int materialise_ncon(ps_env* E, void* stream) {
+  const bool cap = capturing(stream);
+  if (!E->ncon_stale && !E->ncon_sticky && !cap) return 0;
+  const Cfg cfg = make_cfg(E);
+  const Bufs b = make_bufs(E);
+  if (E->has_x)
+    hipLaunchKernelGGL((pianosim_ncon_kernel<true>), dim3(E->n), dim3(64), 0, (hipStream_t)stream,
+                       E->d_model, cfg, b, E->n);
+  else
+    hipLaunchKernelGGL((pianosim_ncon_kernel<false>), dim3(E->n), dim3(64), 0, (hipStream_t)stream,
+                       E->d_model, cfg, b, E->n);
+  HIPCHK(hipGetLastError());
+  if (!cap) E->ncon_stale = false;
+  return 0;
+}
+
+// a step or reset launch is on the stream: without contact recording it may have skipped the
+// final-state collision pass. Captured into a graph, it sets no flag at its replays: from then on
+// the counts are taken as stale for good (every read runs the pass)
+static void mark_ncon(ps_env* E, void* stream) {
+  if (E->con_out) return;
+  E->ncon_stale = true;
+  if (capturing(stream)) E->ncon_sticky = true;
+}
+
+static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask, float* obs, float* reward,
+                  float* discount, uint8_t* step_type, void* stream) {
+  Song song{E->T, E->d_goal, E->d_count, E->d_keys, E->d_fingers, 0, nullptr};
+  if (E->aug_on) {
+    song = Song{E->T, E->aug.goal, E->aug.count, E->aug.keys, E->aug.fingers, E->aug.T_cap, E->aug.T};
+    if (launch_builder(E, mode == 1 ? AUG_RESET : AUG_STEP, mask, nullptr, nullptr, nullptr, stream)) return -1;
+  }
+  const Cfg cfg = make_cfg(E);
+  const Bufs b = make_bufs(E);
   // the time-sliced step: a launch of more envs than resident slots (below that every env has a
   // slot of its own from the start and there is no second round to balance), or every step
   // when PIANOSIM_CHUNKS says so
@@ -402,6 +458,7 @@ static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask,
 #undef PS_LAUNCH_Q
 #endif
     HIPCHK(hipGetLastError());
+    mark_ncon(E, stream);
     return E->keybits ? launch_midi(E, stream) : 0;
   }
   const int* order = nullptr;
@@ -424,6 +481,7 @@ static int launch(ps_env* E, int mode, const float* action, const uint8_t* mask,
   }
 #undef PS_LAUNCH
   HIPCHK(hipGetLastError());
+  mark_ncon(E, stream);
   return E->keybits ? launch_midi(E, stream) : 0;
 }
 
@@ -455,6 +513,7 @@ int ps_set_state(ps_env* E, const float* qpos, const float* qvel, const float* q
                  const float* sustain, const int32_t* t_idx, const uint8_t* last, void* stream) {
   if (!E) return fail("null env");
   GUARD(E);
+  if (materialise_ncon(E, stream)) return -1;  // (the counts of the state about to be overwritten)
   const size_t N = E->n;
   return -(copy_dd(E->qpos, qpos, N * NV, stream) || copy_dd(E->qvel, qvel, N * NV, stream) ||
            copy_dd(E->qws, qacc_ws, N * NV, stream) || copy_dd(E->ctrl, ctrl, N * NU, stream) ||
@@ -545,6 +604,7 @@ int ps_set_hand_offset(ps_env* E, const float* dy, void* stream) {
   if (!E || !dy) return fail("null argument");
   GUARD(E);
   if (!E->cfg.randomize_hand_positions) return fail("ps_set_hand_offset needs randomize_hand_positions");
+  if (materialise_ncon(E, stream)) return -1;  // (the counts of the last launch's hand positions)
   return copy_dd(E->hand_dy, dy, (size_t)E->n, stream);
 }
 
@@ -815,6 +875,7 @@ int ps_episode_returns(const float* reward, const uint8_t* step_type, int n, dou
 int ps_contact_count(ps_env* E, int32_t* ncon, void* stream) {
   if (!E || !ncon) return fail("null argument");
   GUARD(E);
+  if (materialise_ncon(E, stream)) return -1;
   return copy_dd(ncon, E->ncon, (size_t)E->n, stream);
 }
 

@@ -343,7 +343,11 @@ int ps_set_applied(ps_env* env, const float* qfrc_applied, void* stream);
 int ps_reward_terms(ps_env* env, float* terms, void* stream);
 /* Fingertip site positions after the last step/reset, [N][2][5][3] (right, left). */
 int ps_fingertips(ps_env* env, float* xpos, void* stream);
-/* Number of contacts after the last step/reset, [N]. */
+/* Number of contacts after the last step/reset, [N]. Without contact recording a step or reset
+ * runs the final-state collision pass only for the envs whose forearm term needs it; the counts
+ * are then computed here, by one launch of that pass over the state rows (as ps_set_state and
+ * ps_set_hand_offset do before they overwrite what it reads). Captured into a graph, the call
+ * always includes that launch. */
 int ps_contact_count(ps_env* env, int32_t* ncon, void* stream);
 
 /* One contact of the task layer's final collision pass (physics.data.contact after the step):

@@ -35,6 +35,8 @@ for i, n in names.items():
     v = out[:, i].astype(np.float64)
     print(f"{n:14s} {v.mean()/10:12.0f} cycles/env-step  {100*v.sum()/tot.sum():5.1f}%")
 print(f"total {tot.mean()/10:.0f} cycles/env-step per wave; mean rows/substep {out[:,9].mean()/100:.1f} mean contacts {out[:,10].mean()/100:.2f}")
+if out[:, 52].sum() > 0:  # (env-steps, and those whose forearm prefilter passed nothing: no final collide pass)
+    print(f"final-state collide pass skipped in {100 * out[:, 53].sum() / out[:, 52].sum():.2f}% of {int(out[:, 52].sum())} env-steps")
 solves = st[..., 0] / 10.0
 print(f"Newton: iterations per substep mean {solves.mean():.3f}, max over env-steps {st[..., 0].max()} per step; "
       f"contact-cap substeps {int(st[..., 1].sum())}, iteration-cap substeps {int(st[..., 2].sum())}, "
