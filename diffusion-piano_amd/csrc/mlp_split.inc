@@ -497,7 +497,8 @@ __global__ void __launch_bounds__(ST) mlp_split_kernel(Args a) {
     for (int r = 0; r < 4; r++) Zf[(4 * q + r) * HS + n0] = v[r];
     hand_put(H, 0, 16 * wave, v, lane);
   }
-  if (ni == 0 && sp == 0 && sr >= 0) {  // the gathered state rows, for the weight gradient
+  if (a.Sg && ni == 0 && sp == 0 && sr >= 0) {  // the gathered state rows, for the weight gradient
+    // (idx set only: prl_mlp_step passes no Sg, its weight gradient reads S itself)
     float* Sg = a.Sg + (size_t)(r0 + rr_) * sdim;
 #pragma unroll
     for (int u = 0; u < SG; u++)

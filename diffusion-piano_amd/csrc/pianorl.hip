@@ -899,6 +899,9 @@ int mlp_step(const prl_net* nets, const float* S, int sdim, const float* A, int 
   if (mlp_layout(nets, sdim, B, work, log_row, &a, &g, &need)) return -1;
   if (nets[0].layer[3].out != adim) return fail("prl_mlp_step: actor output width != action dim");
   if (work_floats < need) return fail("prl_mlp_step: work space too small (prl_mlp_step_work)");
+  // the split kernel's granules: 8-byte stores that must not tear, read back in 16-byte pairs
+  if (a.hand && (reinterpret_cast<uintptr_t>(work) & 15))
+    return fail("prl_mlp_step: work must be 16-byte aligned at the column-split kernel's shapes");
   const size_t lds = mlp::lds_floats(((sdim + 15) & ~15) + 4) * sizeof(float);
   if (lds > 150 * 1024) return fail("prl_mlp_step: state too wide for the LDS tile");
   a.nnets = 2;

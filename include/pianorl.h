@@ -146,7 +146,24 @@ int prl_colsums(int n, const float* const* src, const int* cols, const float* sc
  * that kernel's error word (0, or 1 + the exchange whose bounded wait timed out) unless a
  * guard is given (see the ABI note above). Test hooks, read per call: PIANORL_SPLIT_SPIN_TICKS
  * (the bounded wait, 100 MHz ticks, default 2 s) and PIANORL_SPLIT_TEST_FAULT=1 (one member
- * never publishes its first exchange, so the others time out). */
+ * never publishes its first exchange, so the others time out).
+ *
+ * Alignment. The kernels read weight rows with 16-byte loads, so for every layer whose input is
+ * a hidden layer (layers 1..3: in = a multiple of 16) W must be 16-byte aligned (ppo.py's flat
+ * buffers start every tensor on a 64-byte boundary, FLAT_ALIGN, for this); a misaligned W there
+ * is undefined behaviour, not an error. Layer 0 (in = the state width, any value) tolerates a W
+ * that is only 4-byte aligned, with any state width, and is never read past the 16-byte word
+ * that holds its last float: the one-workgroup-per-tile kernel reads the aligned 16-byte words
+ * around each four floats of a row (single floats in the row's last partial block), the
+ * column-split kernel reads the full 16-float blocks of a row with 16-byte loads at 4-byte
+ * aligned addresses, inside the row, and the last block as single floats.
+ * work must be 16-byte aligned (any hipMalloc'd pointer is): at the column-split kernel's shapes
+ * its tail holds the exchange granules, written with 8-byte stores that must not tear and read
+ * back 16 bytes at a time; a misaligned work is refused there with an error. norm_part is read
+ * back by prl_clip_adam_parts with 16-byte loads and needs the same. Everything else (biases,
+ * LayerNorm parameters, log_std, S / A / old_lp / adv / ret, every gradient pointer) needs
+ * float alignment only.
+ * State widths up to 400 are accepted (the LDS tile); wider ones are refused with an error. */
 typedef struct {
   int in, out;
   const float *W, *b, *gamma, *beta;  /* W [out][in]; gamma/beta: NULL on the output layer */

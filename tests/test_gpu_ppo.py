@@ -13,6 +13,11 @@
   Tolerance: 2e-4 relative on the logged scalars (5e-4 absolute on the actor loss, whose
   importance ratio exponentiates log-prob differences; fp32
   GPU GEMMs vs fp32 CPU GEMMs), parameter deltas within 2% of each tensor's largest delta.
+
+The kernels one by one (prl_lnrelu_*, the heads, prl_colsums, prl_gather_minibatch,
+prl_gauss_sample's Philox words, prl_clip_adam*, prl_mlp_step* at hidden widths below 256, other
+action widths, B < 16 and under dropout) are held to an independent float64 reference in
+tests/test_gpu_ppo_kernels.py.
 """
 import importlib
 
