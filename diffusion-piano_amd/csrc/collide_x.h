@@ -22,8 +22,10 @@ struct XShape {
   int v0, nv;      // hull vertices in DevModel::hull_v (geom frame)
   f3 e0, e1;       // hull: an enclosing capsule (world), radius er
   float er;
-  const uint64_t* cells;  // hull: its support cells (DevModel::x_cell), or nullptr: scan all vertices
-  const float4* cellv;    // hull: its support-cell vertex table (DevModel::x_cellv), or nullptr
+  // (both tables, and the model `m` of the support functions below, are in global memory, and
+  // typed so: their reads are global_load also in an out-of-line function, see prims.h PS_GLB)
+  const PS_GLB uint64_t* cells;  // hull: its support cells (DevModel::x_cell), or nullptr: scan all vertices
+  const PS_GLB f4g* cellv;       // hull: its support-cell vertex table (DevModel::x_cellv), or nullptr
   float tie;              // hull: SUP_TIE_HULL x its max vertex norm (x_support's tie band)
 };
 
@@ -105,6 +107,7 @@ __device__ __forceinline__ int hull_cell(f3 d) {
 __device__ __forceinline__ float sgn_tie(float x, float band) { return fabsf(x) <= band ? 0.f : sgn0f(x); }
 // box / hull: the support in the collider's own frame (box corner, hull vertex)
 __device__ __forceinline__ f3 x_support_local(const DevModel* __restrict__ m, const XShape& s, f3 d) {
+  const PS_GLB float(*hull_v)[4] = ((const PS_GLB DevModel*)m)->hull_v;
   const f3 dl = mtv3(s.R, d);
   f3 loc;
   if (s.type == PS_GEOM_BOX) {
@@ -115,8 +118,8 @@ __device__ __forceinline__ f3 x_support_local(const DevModel* __restrict__ m, co
     // candidates as x_cell's mask, in the same order, padded by repeats): the cell's 128 bytes
     // in one round of reads, then the same compares as the mask scan below - the same vertex
     const bool zero = dl.x == 0.f && dl.y == 0.f && dl.z == 0.f;
-    const float4* t = s.cellv + (zero ? XNCELL : hull_cell(dl)) * XCV;
-    float4 v[XCV];
+    const PS_GLB f4g* t = s.cellv + (zero ? XNCELL : hull_cell(dl)) * XCV;
+    f4g v[XCV];
 #pragma unroll
     for (int u = 0; u < XCV; u++) v[u] = t[u];
     const float tie = s.tie * norm3(dl);
@@ -145,7 +148,7 @@ __device__ __forceinline__ f3 x_support_local(const DevModel* __restrict__ m, co
         ok[u] = msk != 0ull;
         const int id = ok[u] ? __builtin_ctzll(msk) : 0;
         msk &= msk - 1ull;
-        const float4 q = *reinterpret_cast<const float4*>(m->hull_v[s.v0 + id]);
+        const f4g q = *reinterpret_cast<const PS_GLB f4g*>(hull_v[s.v0 + id]);
         v[u] = mk3(q.x, q.y, q.z);
       }
 #pragma unroll
@@ -161,9 +164,9 @@ __device__ __forceinline__ f3 x_support_local(const DevModel* __restrict__ m, co
     float bd = -INFINITY;
     loc = mk3(0.f, 0.f, 0.f);
     for (int i0 = 0; i0 < s.nv; i0 += 8) {
-      float4 v[8];
+      f4g v[8];
 #pragma unroll
-      for (int j = 0; j < 8; j++) v[j] = *reinterpret_cast<const float4*>(m->hull_v[s.v0 + min(i0 + j, s.nv - 1)]);
+      for (int j = 0; j < 8; j++) v[j] = *reinterpret_cast<const PS_GLB f4g*>(hull_v[s.v0 + min(i0 + j, s.nv - 1)]);
 #pragma unroll
       for (int j = 0; j < 8; j++) {
         const float p = fmaf(dl.z, v[j].z, fmaf(dl.y, v[j].y, dl.x * v[j].x));
@@ -229,13 +232,12 @@ __device__ __forceinline__ bool portal_reach_tol(const MprPt& p1, const MprPt& p
   const float mn = fminf(d4 - dot3(p1.v, dir), fminf(d4 - dot3(p2.v, dir), d4 - dot3(p3.v, dir)));
   return mn <= MPR_TOLF;
 }
-__device__ __forceinline__ void expand_portal(const MprPt& p0, MprPt& p1, MprPt& p2, MprPt& p3, const MprPt& v4) {
+// the portal point (1..3) that v4 replaces when the portal expands (libccd's ccdMPRExpandPortal)
+__device__ __forceinline__ int expand_portal_idx(const MprPt& p0, const MprPt& p1, const MprPt& p2, const MprPt& p3,
+                                                 const MprPt& v4) {
   const f3 v4v0 = cross3(v4.v, p0.v);
-  if (dot3(p1.v, v4v0) > 0.f) {
-    if (dot3(p2.v, v4v0) > 0.f) p1 = v4; else p3 = v4;
-  } else {
-    if (dot3(p3.v, v4v0) > 0.f) p2 = v4; else p1 = v4;
-  }
+  if (dot3(p1.v, v4v0) > 0.f) return dot3(p2.v, v4v0) > 0.f ? 1 : 3;
+  return dot3(p3.v, v4v0) > 0.f ? 2 : 1;
 }
 // closest point of triangle (a, b, c) to the origin (Ericson, RTCD 5.1.5), in fp64: MPR's final
 // portal is a small triangle (sub-mm edges) ~1 mm from the origin, and the fp32 form's
@@ -314,46 +316,67 @@ __device__ __forceinline__ int mpr_penetration(const DevModel* __restrict__ m, c
   if (mpr_zero(dt) || dt < 0.f) return 0;
   dir = nrmz3(cross3(p1.v - p0.v, p2.v - p0.v));
   if (dot3(dir, p0.v) > 0.f) { const MprPt t = p1; p1 = p2; p2 = t; dir = dir * -1.f; }
+  // The checker's three loops - 0: discovery (a p3 with the origin ray inside (p0; p1, p2, p3)),
+  // 1: portal search (the portal pushed out until the origin is behind it), 2: refinement - as ONE
+  // loop with one support search: the same statements on the same operands in the same order per
+  // pair, one copy of the support code instead of three, and lanes of a wave in different phases
+  // share a trip. (The same source statements, not the same bits: the compiler fuses multiply-adds
+  // per inlined copy. With this file's and prims.h's vector arithmetic under fp contract(off) the
+  // three-loop form and this one give bitwise the same benchmark outputs; as built, 2 of 4096 envs
+  // differ after 35 steps - DESIGN.md section 5, round 11.) `it` counts the trips of the phase.
+  // The point v4
+  // replaces is chosen as an index, the portal then written once (selects by value, as put3:
+  // a store through a selected address would put the portal in scratch).
+  int phase = 0;
   for (int it = 0;; it++) {
-    if (its) ++*its;  // (timing build: support calls of the refinement)
-    if (it > 4 * MPR_MAXITF) return 0;
-    p3 = mpr_sup_t<PAIR>(m, A, B, own, role, dir);
-    dt = dot3(p3.v, dir);
-    if (mpr_zero(dt) || dt < 0.f) return 0;
-    bool cont = false;
-    float t = dot3(cross3(p1.v, p3.v), p0.v);
-    if (t < 0.f && !mpr_zero(t)) { p2 = p3; cont = true; }
-    if (!cont) {
-      t = dot3(cross3(p3.v, p2.v), p0.v);
-      if (t < 0.f && !mpr_zero(t)) { p1 = p3; cont = true; }
+    if (its) ++*its;  // (timing build: trips of the three phases)
+    if (phase != 2 && it > 4 * MPR_MAXITF) return 0;
+    if (phase != 0) {
+      dir = portal_dir(p1, p2, p3);
+      if (phase == 1) {
+        dt = dot3(p1.v, dir);
+        if (mpr_zero(dt) || dt > 0.f) {  // found: this is refinement's first trip (same portal, same dir)
+          phase = 2;
+          it = 0;
+          if (its) ++*its;
+        }
+      }
     }
-    if (!cont) break;
-    dir = nrmz3(cross3(p1.v - p0.v, p2.v - p0.v));
-  }
-  for (int it = 0;; it++) {
-    if (its) ++*its;  // (timing build: support calls of the refinement)
-    if (it > 4 * MPR_MAXITF) return 0;
-    dir = portal_dir(p1, p2, p3);
-    dt = dot3(p1.v, dir);
-    if (mpr_zero(dt) || dt > 0.f) break;
     const MprPt v4 = mpr_sup_t<PAIR>(m, A, B, own, role, dir);
-    const float d4 = dot3(v4.v, dir);
-    if (!(mpr_zero(d4) || d4 > 0.f) || portal_reach_tol(p1, p2, p3, v4, dir)) return 0;
-    expand_portal(p0, p1, p2, p3, v4);
-  }
-  for (int it = 0;; it++) {
-    if (its) ++*its;  // (timing build: support calls of the refinement)
-    dir = portal_dir(p1, p2, p3);
-    const MprPt v4 = mpr_sup_t<PAIR>(m, A, B, own, role, dir);
-    if (portal_reach_tol(p1, p2, p3, v4, dir) || it > MPR_MAXITF) {
-      const f3 cp = tri_closest_origin_d(p1.v, p2.v, p3.v);
-      *depth = norm3(cp);
-      *n = mpr_zero(*depth) ? dir : cp * (1.f / *depth);
-      *pos = mpr_pos(p0, p1, p2, p3);
-      return 1;
+    const bool disc = phase == 0;
+    int rp = 3;
+    if (disc) {
+      dt = dot3(v4.v, dir);
+      if (mpr_zero(dt) || dt < 0.f) return 0;
+      float t = dot3(cross3(p1.v, v4.v), p0.v);
+      if (t < 0.f && !mpr_zero(t)) rp = 2;
+      else {
+        t = dot3(cross3(v4.v, p2.v), p0.v);
+        if (t < 0.f && !mpr_zero(t)) rp = 1;
+      }
+    } else {
+      const bool reach = portal_reach_tol(p1, p2, p3, v4, dir);
+      if (phase == 1) {
+        const float d4 = dot3(v4.v, dir);
+        if (!(mpr_zero(d4) || d4 > 0.f) || reach) return 0;
+      } else if (reach || it > MPR_MAXITF) {
+        break;
+      }
+      rp = expand_portal_idx(p0, p1, p2, p3, v4);
     }
-    expand_portal(p0, p1, p2, p3, v4);
+    if (rp == 1) p1 = v4;
+    if (rp == 2) p2 = v4;
+    if (rp == 3 || disc) p3 = v4;
+    if (disc) {
+      if (rp == 3) { phase = 1; it = -1; }
+      else dir = nrmz3(cross3(p1.v - p0.v, p2.v - p0.v));
+    }
   }
+  const f3 cp = tri_closest_origin_d(p1.v, p2.v, p3.v);
+  *depth = norm3(cp);
+  *n = mpr_zero(*depth) ? dir : cp * (1.f / *depth);
+  *pos = mpr_pos(p0, p1, p2, p3);
+  return 1;
 }
 
 // ------------------------------------------------------------------ MPR in fp64 (PS_MPR_F64)
@@ -452,13 +475,11 @@ __device__ __forceinline__ bool portal_reach_tol_d(const MprPtD& p1, const MprPt
   const double d4 = dotd(v4.v, dir);
   return fmin(d4 - dotd(p1.v, dir), fmin(d4 - dotd(p2.v, dir), d4 - dotd(p3.v, dir))) <= 1e-6;  // (the checker's MPR_TOL)
 }
-__device__ __forceinline__ void expand_portal_d(const MprPtD& p0, MprPtD& p1, MprPtD& p2, MprPtD& p3, const MprPtD& v4) {
+__device__ __forceinline__ int expand_portal_idx_d(const MprPtD& p0, const MprPtD& p1, const MprPtD& p2, const MprPtD& p3,
+                                                   const MprPtD& v4) {
   const d3 v4v0 = crossd(v4.v, p0.v);
-  if (dotd(p1.v, v4v0) > 0.0) {
-    if (dotd(p2.v, v4v0) > 0.0) p1 = v4; else p3 = v4;
-  } else {
-    if (dotd(p3.v, v4v0) > 0.0) p2 = v4; else p1 = v4;
-  }
+  if (dotd(p1.v, v4v0) > 0.0) return dotd(p2.v, v4v0) > 0.0 ? 1 : 3;
+  return dotd(p3.v, v4v0) > 0.0 ? 2 : 1;
 }
 __device__ __forceinline__ d3 tri_closest_origin_dd(d3 a, d3 b, d3 c) {
   const d3 ab = b - a, ac = c - a;
@@ -520,47 +541,58 @@ __device__ __forceinline__ int mpr_penetration_d(const DevModel* __restrict__ m,
   if (mpr_zerod(dt) || dt < 0.0) return 0;
   dir = nrmzd(crossd(p1.v - p0.v, p2.v - p0.v));
   if (dotd(dir, p0.v) > 0.0) { const MprPtD t = p1; p1 = p2; p2 = t; dir = dir * -1.0; }
+  // (one loop over the three phases with one support search: see mpr_penetration)
+  int phase = 0;
   for (int it = 0;; it++) {
     if (its) ++*its;
-    if (it > 4 * MPR_MAXITF) return 0;
-    p3 = mpr_sup_d<PAIR>(m, A, B, own, role, dir);
-    dt = dotd(p3.v, dir);
-    if (mpr_zerod(dt) || dt < 0.0) return 0;
-    bool cont = false;
-    double t = dotd(crossd(p1.v, p3.v), p0.v);
-    if (t < 0.0 && !mpr_zerod(t)) { p2 = p3; cont = true; }
-    if (!cont) {
-      t = dotd(crossd(p3.v, p2.v), p0.v);
-      if (t < 0.0 && !mpr_zerod(t)) { p1 = p3; cont = true; }
+    if (phase != 2 && it > 4 * MPR_MAXITF) return 0;
+    if (phase != 0) {
+      dir = portal_dir_d(p1, p2, p3);
+      if (phase == 1) {
+        dt = dotd(p1.v, dir);
+        if (mpr_zerod(dt) || dt > 0.0) {
+          phase = 2;
+          it = 0;
+          if (its) ++*its;
+        }
+      }
     }
-    if (!cont) break;
-    dir = nrmzd(crossd(p1.v - p0.v, p2.v - p0.v));
-  }
-  for (int it = 0;; it++) {
-    if (its) ++*its;
-    if (it > 4 * MPR_MAXITF) return 0;
-    dir = portal_dir_d(p1, p2, p3);
-    dt = dotd(p1.v, dir);
-    if (mpr_zerod(dt) || dt > 0.0) break;
     const MprPtD v4 = mpr_sup_d<PAIR>(m, A, B, own, role, dir);
-    const double d4 = dotd(v4.v, dir);
-    if (!(mpr_zerod(d4) || d4 > 0.0) || portal_reach_tol_d(p1, p2, p3, v4, dir)) return 0;
-    expand_portal_d(p0, p1, p2, p3, v4);
-  }
-  for (int it = 0;; it++) {
-    if (its) ++*its;
-    dir = portal_dir_d(p1, p2, p3);
-    const MprPtD v4 = mpr_sup_d<PAIR>(m, A, B, own, role, dir);
-    if (portal_reach_tol_d(p1, p2, p3, v4, dir) || it > MPR_MAXITF) {
-      const d3 cp = tri_closest_origin_dd(p1.v, p2.v, p3.v);
-      const double dep = sqrt(dotd(cp, cp));
-      *depth = (float)dep;
-      *n = tof3(mpr_zerod(dep) ? dir : cp * (1.0 / dep));
-      *pos = tof3(mpr_pos_d(p0, p1, p2, p3));
-      return 1;
+    const bool disc = phase == 0;
+    int rp = 3;
+    if (disc) {
+      dt = dotd(v4.v, dir);
+      if (mpr_zerod(dt) || dt < 0.0) return 0;
+      double t = dotd(crossd(p1.v, v4.v), p0.v);
+      if (t < 0.0 && !mpr_zerod(t)) rp = 2;
+      else {
+        t = dotd(crossd(v4.v, p2.v), p0.v);
+        if (t < 0.0 && !mpr_zerod(t)) rp = 1;
+      }
+    } else {
+      const bool reach = portal_reach_tol_d(p1, p2, p3, v4, dir);
+      if (phase == 1) {
+        const double d4 = dotd(v4.v, dir);
+        if (!(mpr_zerod(d4) || d4 > 0.0) || reach) return 0;
+      } else if (reach || it > MPR_MAXITF) {
+        break;
+      }
+      rp = expand_portal_idx_d(p0, p1, p2, p3, v4);
     }
-    expand_portal_d(p0, p1, p2, p3, v4);
+    if (rp == 1) p1 = v4;
+    if (rp == 2) p2 = v4;
+    if (rp == 3 || disc) p3 = v4;
+    if (disc) {
+      if (rp == 3) { phase = 1; it = -1; }
+      else dir = nrmzd(crossd(p1.v - p0.v, p2.v - p0.v));
+    }
   }
+  const d3 cp = tri_closest_origin_dd(p1.v, p2.v, p3.v);
+  const double dep = sqrt(dotd(cp, cp));
+  *depth = (float)dep;
+  *n = tof3(mpr_zerod(dep) ? dir : cp * (1.0 / dep));
+  *pos = tof3(mpr_pos_d(p0, p1, p2, p3));
+  return 1;
 }
 
 // ------------------------------------------------------------------ box-box

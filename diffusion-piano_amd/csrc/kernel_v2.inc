@@ -14,6 +14,8 @@
 #ifdef PS_TIMING
 #define NPHASE 56
 enum : int { TS_FINAL = 52, TS_FINAL_SKIP = 53 };  // counters: env-steps, and those without the final collide pass
+// counters: box / hull narrow-phase rounds with both an MPR and a capsule-box / box-box pair; without a touching pair
+enum : int { TS_XMIXED = 54, TS_XNOHIT = 55 };
 #define TARG , uint64_t *tacc, uint64_t &tlast
 #define TPASS , tacc, tlast
 #define TSTAMP(slot)                                     \
@@ -297,7 +299,9 @@ __device__ __forceinline__ int xpiano_candidates(const DevModel* __restrict__ m,
   return n + 1;
 }
 
-__device__ __forceinline__ XShape coll_shape(const DevModel* __restrict__ m, const Shared& S, int g) {
+// (m, S: the model and the workgroup's LDS through typed pointers, prims.h PS_GLB / PS_LDS - the
+// callers are out of line, where a generic pointer's reads would be flat_loads)
+__device__ __forceinline__ XShape coll_shape(const PS_GLB DevModel* m, const PS_LDS Shared* S, int g) {
   XShape s;
   s.cells = nullptr;
   s.cellv = nullptr;
@@ -308,9 +312,9 @@ __device__ __forceinline__ XShape coll_shape(const DevModel* __restrict__ m, con
   s.hs = mk3(0.f, 0.f, 0.f);
   if (g < NGT) {
     s.type = 0;
-    s.p0 = ld3(&S.cap[g][0]);
-    s.p1 = ld3(&S.cap[g][3]);
-    s.r = S.cap[g][6];
+    s.p0 = ld3(&S->cap[g][0]);
+    s.p1 = ld3(&S->cap[g][3]);
+    s.r = S->cap[g][6];
     s.c = (s.p0 + s.p1) * 0.5f;
     s.e0 = s.e1 = s.c;
 #pragma unroll
@@ -318,16 +322,16 @@ __device__ __forceinline__ XShape coll_shape(const DevModel* __restrict__ m, con
   } else {
     const int e = g - NGT;
     s.type = m->x_type[e];
-    s.c = ld3(S.xg[e]);
+    s.c = ld3(S->xg[e]);
 #pragma unroll
-    for (int i = 0; i < 9; i++) s.R[i] = S.xg[e][3 + i];
+    for (int i = 0; i < 9; i++) s.R[i] = S->xg[e][3 + i];
     s.hs = ld3(m->x_hs[e]);
     s.v0 = m->x_v0[e];
     s.nv = m->x_nv[e];
     s.p0 = s.p1 = s.e0 = s.e1 = s.c;
     if (s.type == PS_GEOM_HULL) {
       s.cells = m->x_cell[e];
-      s.cellv = m->x_cellv_ok[e] ? reinterpret_cast<const float4*>(&m->x_cellv[e][0][0][0]) : nullptr;
+      s.cellv = m->x_cellv_ok[e] ? reinterpret_cast<const PS_GLB f4g*>(&m->x_cellv[e][0][0][0]) : nullptr;
       s.e0 = s.c + mv3(s.R, ld3(&m->x_ec[e][0]));
       s.e1 = s.c + mv3(s.R, ld3(&m->x_ec[e][3]));
       s.er = m->x_ec[e][6];
@@ -347,7 +351,7 @@ __device__ __forceinline__ XShape coll_shape(const DevModel* __restrict__ m, con
 // copy of the narrow phases for the piano and the hand-hand call sites.
 // The two colliders of a box / hull pair (x_pairs' argument meaning): geom1 A is the key / base
 // box (ga < 0) or hand collider ga, geom2 B is hand collider gb.
-__device__ __forceinline__ void x_pair_shapes(const DevModel* __restrict__ m, const Shared& S, int ga, int gb, int key,
+__device__ __forceinline__ void x_pair_shapes(const PS_GLB DevModel* m, const PS_LDS Shared* S, int ga, int gb, int key,
                                               XShape& A, XShape& B, int& kind, int& ckey) {
   B = coll_shape(m, S, gb);
   kind = 2;
@@ -367,8 +371,8 @@ __device__ __forceinline__ void x_pair_shapes(const DevModel* __restrict__ m, co
     } else {
       kind = 0;
       ckey = key;
-      const float* g = S.kg[key];
-      const float cq = S.kc[key], sq = S.ks[key];
+      const PS_LDS float* g = S->kg[key];
+      const float cq = S->kc[key], sq = S->ks[key];
       const float R[9] = {cq, 0.f, sq, 0.f, 1.f, 0.f, -sq, 0.f, cq};
 #pragma unroll
       for (int i = 0; i < 9; i++) A.R[i] = R[i];
@@ -406,24 +410,25 @@ __device__ __forceinline__ void x_entry(int pk, int& ga, int& gb, int& key) {
 // (WPE: the calling kernel instantiation's waves per SIMD - each instantiation gets its own
 // out-of-line copy, compiled to its register budget)
 template <int WPE>
-__device__ PS_XREFINE_ATTR int x_refine(const DevModel* __restrict__ m, const Shared* Sp, uint16_t* list, int n,
+// (the address spaces are in the parameter types - the model in global memory, the workgroup's
+// Shared and the list in LDS: a caller with anything else does not compile)
+__device__ PS_XREFINE_ATTR int x_refine(const PS_GLB DevModel* mg, const PS_LDS Shared* S, PS_LDS uint16_t* ll, int n,
                                      int lane) {
-  const Shared& S = *Sp;
   int kept = 0;
   for (int r0 = 0; r0 < n; r0 += 64) {
     const int i = r0 + lane;
-    const int pk = i < n ? (int)list[i] : 0;
+    const int pk = i < n ? (int)ll[i] : 0;
     bool keep = false;
     if (i < n) {
       XShape A, B;
       int kind, ckey, ga, gb, key;
       x_entry(pk, ga, gb, key);
-      x_pair_shapes(m, S, ga, gb, key, A, B, kind, ckey);
+      x_pair_shapes(mg, S, ga, gb, key, A, B, kind, ckey);
       keep = !x_apart(A, B);
     }
     const uint64_t mask = __ballot(keep);
     wsync();
-    if (keep) list[kept + lanes_below(mask, lane)] = (uint16_t)pk;
+    if (keep) ll[kept + lanes_below(mask, lane)] = (uint16_t)pk;
     kept += __popcll(mask);
     wsync();
   }
@@ -431,14 +436,14 @@ __device__ PS_XREFINE_ATTR int x_refine(const DevModel* __restrict__ m, const Sh
 }
 
 template <int WPE>
-__device__ PS_XPAIRS_ATTR int x_pairs(const DevModel* __restrict__ m, const Shared* Sp, bool act, int ga, int gb, int key,
+__device__ PS_XPAIRS_ATTR int x_pairs(const PS_GLB DevModel* mg, const PS_LDS Shared* S, bool act, int ga, int gb, int key,
                                     Contact* out, int base, int maxc, int lane,
                                     int* its = nullptr) {
-  const Shared& S = *Sp;
   if (!act) { ga = -1; gb = NGT; key = BASEKEY; }  // (inert shapes; the count is forced to 0)
   XShape A, B;
   int kind, ckey;
-  x_pair_shapes(m, S, ga, gb, key, A, B, kind, ckey);
+  x_pair_shapes(mg, S, ga, gb, key, A, B, kind, ckey);
+  const DevModel* m = (const DevModel*)mg;  // (the support functions of collide_x.h type their own reads)
   int g1 = ga < 0 ? -1 : ga, g2 = gb;
   f3 pos[BB_MAXPT], nrm[BB_MAXPT];
   float dist[BB_MAXPT];
@@ -453,6 +458,13 @@ __device__ PS_XPAIRS_ATTR int x_pairs(const DevModel* __restrict__ m, const Shar
     its[2] = __popcll(__ballot(act && !role && cnt > 0));
     its[3] = wave_sum_i(act && !role ? nit : 0);
     its[4] = wave_sum_i(act && !role && cnt > 0 ? nit : 0);
+#ifdef PS_TIMING
+    // the round holds both an MPR pair and a capsule-box / box-box pair (x_narrow runs every kind
+    // present, one after the other); no pair of the round touches
+    const bool mpr = !((A.type == 0 || A.type == PS_GEOM_BOX) && B.type == PS_GEOM_BOX);
+    its[5] = __ballot(act && mpr) != 0ull && __ballot(act && !mpr) != 0ull;
+    its[6] = __ballot(act && !role && cnt > 0) == 0ull;
+#endif
   }
   if (role) cnt = 0;
   if (swap) {  // capsule (geom a) vs box (geom b): the box is geom1
@@ -723,7 +735,10 @@ __device__ __forceinline__ int collide2(const DevModel* __restrict__ m, Shared& 
     }
     wsync();
     TSTAMP(35);
-    nl = x_refine<WPE>(m, &S, cand, nl, lane);
+    // (the out-of-line narrow phases take typed pointers: S is the workgroup's LDS, m the kernel's model argument)
+    const PS_GLB DevModel* mg = (const PS_GLB DevModel*)m;
+    const PS_LDS Shared* Sl = (const PS_LDS Shared*)&S;
+    nl = x_refine<WPE>(mg, Sl, (PS_LDS uint16_t*)cand, nl, lane);
 #ifdef PS_TIMING
     tacc[42] += nl > 0;
 #endif
@@ -733,16 +748,18 @@ __device__ __forceinline__ int collide2(const DevModel* __restrict__ m, Shared& 
       int ga, gb, key;
       x_entry(q < nl ? (int)cand[q] : 0, ga, gb, key);
 #ifdef PS_TIMING
-      int its[5] = {0, 0, 0, 0, 0};
-      base += x_pairs<WPE>(m, &S, q < nl, ga, gb, key, S.con, base, maxc, lane, its);
+      int its[7] = {0, 0, 0, 0, 0, 0, 0};
+      base += x_pairs<WPE>(mg, Sl, q < nl, ga, gb, key, S.con, base, maxc, lane, its);
       tacc[30] += its[0];
       tacc[31] += 1;
       tacc[38] += its[1];
       tacc[39] += its[2];
       tacc[40] += its[3];
       tacc[41] += its[4];
+      tacc[TS_XMIXED] += its[5];
+      tacc[TS_XNOHIT] += its[6];
 #else
-      base += x_pairs<WPE>(m, &S, q < nl, ga, gb, key, S.con, base, maxc, lane);
+      base += x_pairs<WPE>(mg, Sl, q < nl, ga, gb, key, S.con, base, maxc, lane);
 #endif
     }
     TSTAMP(37);

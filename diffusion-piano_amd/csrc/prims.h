@@ -22,6 +22,16 @@ struct f3 {
 __device__ __forceinline__ f3 mk3(float a, float b, float c) { return {a, b, c}; }
 __device__ __forceinline__ f3 ld3(const float* p) { return {p[0], p[1], p[2]}; }
 __device__ __forceinline__ void st3(float* p, f3 a) { p[0] = a.x; p[1] = a.y; p[2] = a.z; }
+// Pointers with their address space in the type (LDS, global memory). An out-of-line device
+// function only sees generic pointers, and every read through one is a flat_load: the slow
+// path for LDS, and counted in both wait counters. Reads through a PS_LDS / PS_GLB pointer are
+// ds_read / global_load. The address space has to stay in the type down to the load: a cast to
+// it and back to a generic pointer is folded away.
+#define PS_LDS __attribute__((address_space(3)))
+#define PS_GLB __attribute__((address_space(1)))
+__device__ __forceinline__ f3 ld3(const PS_LDS float* p) { return {p[0], p[1], p[2]}; }
+__device__ __forceinline__ f3 ld3(const PS_GLB float* p) { return {p[0], p[1], p[2]}; }
+typedef float f4g __attribute__((ext_vector_type(4)));  // a float4 that loads through a typed pointer
 __device__ __forceinline__ f3 operator+(f3 a, f3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
 __device__ __forceinline__ f3 operator-(f3 a, f3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ f3 operator*(f3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }

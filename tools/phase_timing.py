@@ -51,6 +51,10 @@ m = out[:, 28:32].astype(np.float64).sum(axis=0)  # box / hull narrow-phase roun
 if m[1] > 0 or m[3] > 0:
     print(f"box/hull narrow phase: piano {m[1] / N / 100:.2f} rounds/substep, {m[0] / max(m[1], 1):.1f} MPR steps of the "
           f"slowest lane per round; piano + hand-hand {m[3] / N / 100:.2f} rounds/substep, {m[2] / max(m[3], 1):.1f} steps")
+    x = out[:, 54:56].astype(np.float64).sum(axis=0)  # (TS_XMIXED, TS_XNOHIT of kernel_v2.inc)
+    if x.sum() > 0:  # (a library from before these counters leaves both slots 0: nothing measured)
+        print(f"box/hull narrow-phase rounds: {100 * x[0] / max(m[3], 1):.2f}% hold both an MPR pair and a capsule-box or "
+              f"box-box pair, {100 * x[1] / max(m[3], 1):.2f}% have no touching pair (of {int(m[3])} rounds)")
 h = out[:, 38:46].astype(np.float64).sum(axis=0)
 if h[0] > 0:
     print(f"box/hull pairs per substep: {h[7] / N / 100:.2f} listed (piano candidates + hand-hand past the spheres), "

@@ -4,8 +4,11 @@
 # out-of-line narrow phases they call (x_pairs, x_refine: part of the caller's scratch), from the
 # code object metadata and symbols of a device-only compile to assembly with the product flags
 # (__graft_entry__._hipcc_lib); and, per kernel and out-of-line function, the static load figures of
-# its assembly: the global_load instructions, and the `s_waitcnt vmcnt` waits with exactly one
-# global_load issued since the previous one (a model-table round trip paid on its own).
+# its assembly: the instructions in all and the v_mov / v_cndmask among them, the global_load and
+# flat_load instructions (a flat_load is a read through a generic pointer: it takes the flat path
+# and counts in both wait counters, where a typed LDS or global pointer gives ds_read /
+# global_load), and the `s_waitcnt vmcnt` waits with exactly one global_load issued since the
+# previous one (a model-table round trip paid on its own).
 # usage: bash tools/resource_usage.sh [extra hipcc flags]
 cd "$(dirname "$0")/.."
 S=$(mktemp /tmp/ps_dev.XXXXXX.s)
@@ -23,6 +26,10 @@ awk '
   # the code of a kernel or function: from its label to its .Lfunc_end
   /^_Z[A-Za-z0-9_]+:/ { cur = $1; sub(/:$/, "", cur); since = 0 }
   /^\.Lfunc_end/ { cur = "" }
+  cur != "" && /^[ \t]+(v|s|ds|flat|global|scratch|buffer)_[a-z0-9_]+/ { insts[cur]++ }
+  cur != "" && /^[ \t]+v_mov_b/ { movs[cur]++ }
+  cur != "" && /^[ \t]+v_cndmask/ { cnds[cur]++ }
+  cur != "" && /^[ \t]+flat_load/ { flats[cur]++ }
   cur != "" && /^[ \t]+global_load/ { loads[cur]++; since++ }
   cur != "" && /^[ \t]+s_waitcnt.*vmcnt\(/ { waits[cur]++; if (since == 1) single[cur]++; since = 0 }
   # kernels: one amdhsa.kernels metadata entry each (its keys are sorted, .agpr_count first)
@@ -42,6 +49,7 @@ awk '
       printf "%s\t(out of line) VGPRs: %s\tframe [bytes/lane]: %s\n", forder[i], fv[forder[i]], fs[forder[i]]
     for (i = 1; i <= nf; i++) lorder[++nl] = forder[i]
     for (i = 1; i <= nl; i++)
-      printf "%s\tglobal_loads: %d\tvmcnt waits: %d\tvmcnt waits after a single global_load: %d\n", lorder[i],
-        loads[lorder[i]], waits[lorder[i]], single[lorder[i]]
+      printf "%s\tinstructions: %d\tv_mov: %d\tv_cndmask: %d\tglobal_loads: %d\tflat_loads: %d\tvmcnt waits: %d\tvmcnt waits after a single global_load: %d\n",
+        lorder[i], insts[lorder[i]], movs[lorder[i]], cnds[lorder[i]], loads[lorder[i]], flats[lorder[i]], waits[lorder[i]],
+        single[lorder[i]]
   }' "$S"

@@ -1,6 +1,7 @@
 // Test harness (not part of the product library): runs the kernel's narrow phase (x_narrow of
 // csrc/collide_x.h) on packed collider pairs, one pair per thread, for a parity check against
-// the CPU checker's ref_narrow (tests/test_gpu_colliders.py). Build: tools/build_xcheck.sh.
+// the CPU checker's ref_narrow (tests/test_gpu_colliders.py; with the trips of each pair's MPR loop:
+// tests/test_gpu_mpr_single_loop.py). Build: tools/build_xcheck.sh.
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -27,8 +28,10 @@ __device__ XShape unpack(const DevModel* m, const float* p, const uint64_t* cell
   s.v0 = (int)p[23];
   s.nv = (int)p[24];
   s.er = 0.f;
-  s.cells = cells && s.type == PS_GEOM_HULL ? cells + (size_t)s.v0 * XNCELL : nullptr;
-  s.cellv = table && s.type == PS_GEOM_HULL && tok[s.v0] ? table + (size_t)s.v0 * (XNCELL + 1) * XCV : nullptr;
+  // (the tables and the model are hipMalloc'ed: global memory, as XShape's pointers say)
+  s.cells = cells && s.type == PS_GEOM_HULL ? (const PS_GLB uint64_t*)cells + (size_t)s.v0 * XNCELL : nullptr;
+  s.cellv = table && s.type == PS_GEOM_HULL && tok[s.v0] ? (const PS_GLB f4g*)table + (size_t)s.v0 * (XNCELL + 1) * XCV
+                                                          : nullptr;
   if (s.type == 0) s.c = (s.p0 + s.p1) * 0.5f;
   s.e0 = s.e1 = s.c;
   float rb = 0.f;  // the hull's max vertex norm (DevModel::x_rb in the step kernel)
@@ -39,9 +42,10 @@ __device__ XShape unpack(const DevModel* m, const float* p, const uint64_t* cell
 
 // paired: the step kernel's paired MPR (x_narrow_local<true>): two threads per pair, lanes 2k
 // and 2k + 1 (role = lane & 1), the even one writes; else one thread per pair
-template <bool PAIR>
+// ITS: also the pair's MPR loop trips (mpr_penetration's `its`) to its[i]
+template <bool PAIR, bool ITS = false>
 __global__ void xcheck_kernel(const DevModel* m, const uint64_t* cells, const float4* table, const int* tok,
-                              const float* a, const float* b, float* out, int n) {
+                              const float* a, const float* b, float* out, int n, int* its = nullptr) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   const int i = PAIR ? t >> 1 : t;
   if (i >= n) return;
@@ -49,8 +53,10 @@ __global__ void xcheck_kernel(const DevModel* m, const uint64_t* cells, const fl
   f3 pos[BB_MAXPT], nrm[BB_MAXPT];
   float dist[BB_MAXPT];
   bool swap;
-  const int cnt = x_narrow_local<PAIR>(m, A, B, pos, dist, nrm, swap, nullptr, t & 1);  // the step kernel's
+  int nit = 0;
+  const int cnt = x_narrow_local<PAIR>(m, A, B, pos, dist, nrm, swap, ITS ? &nit : nullptr, t & 1);  // the step kernel's
   if (PAIR && (t & 1)) return;
+  if (ITS) its[i] = nit;
   float* o = out + i * (1 + 7 * BB_MAXPT);
   o[0] = (float)cnt;
   for (int j = 0; j < BB_MAXPT; j++) {
@@ -60,6 +66,8 @@ __global__ void xcheck_kernel(const DevModel* m, const uint64_t* cells, const fl
     o[7 + 7 * j] = dist[j];
   }
 }
+
+static int run(const float* hull_v, int nv, const float* a, const float* b, float* out, int n, int cells, int* its);
 
 extern "C" {
 // host only (CPU tests): the support cells of one hull, vertices [n][3] -> out [XNCELL]
@@ -76,6 +84,15 @@ int xcheck_cell_grid(void) { return XCG; }
 // threads per pair, as the step kernel); cells & 4 (with & 1): the support-cell vertex tables
 // (DevModel::x_cellv, where no cell overflows them) before the masks
 int xcheck_run(const float* hull_v, int nv, const float* a, const float* b, float* out, int n, int cells) {
+  return run(hull_v, nv, a, b, out, n, cells, nullptr);
+}
+// xcheck_run, and its [n] (device): the trips of each pair's MPR loop (0: no MPR, or over before the loop)
+int xcheck_run_its(const float* hull_v, int nv, const float* a, const float* b, float* out, int n, int cells, int* its) {
+  return run(hull_v, nv, a, b, out, n, cells, its);
+}
+}
+
+static int run(const float* hull_v, int nv, const float* a, const float* b, float* out, int n, int cells, int* its) {
   const bool paired = cells & 2, tables = cells & 4;
   cells &= 1;
   if (nv > NH * PS_HAND_HULLVERT) return -1;
@@ -121,17 +138,22 @@ int xcheck_run(const float* hull_v, int nv, const float* a, const float* b, floa
         return -10;
     }
   }
-  if (paired)
-    hipLaunchKernelGGL(xcheck_kernel<true>, dim3((2 * n + 63) / 64), dim3(64), 0, 0, dm, dcells, dtable, dtok, a, b,
-                       out, n);
+  if (paired && its)
+    hipLaunchKernelGGL((xcheck_kernel<true, true>), dim3((2 * n + 63) / 64), dim3(64), 0, 0, dm, dcells, dtable, dtok, a,
+                       b, out, n, its);
+  else if (paired)
+    hipLaunchKernelGGL((xcheck_kernel<true>), dim3((2 * n + 63) / 64), dim3(64), 0, 0, dm, dcells, dtable, dtok, a, b,
+                       out, n, nullptr);
+  else if (its)
+    hipLaunchKernelGGL((xcheck_kernel<false, true>), dim3((n + 63) / 64), dim3(64), 0, 0, dm, dcells, dtable, dtok, a, b,
+                       out, n, its);
   else
-    hipLaunchKernelGGL(xcheck_kernel<false>, dim3((n + 63) / 64), dim3(64), 0, 0, dm, dcells, dtable, dtok, a, b, out,
-                       n);
+    hipLaunchKernelGGL((xcheck_kernel<false>), dim3((n + 63) / 64), dim3(64), 0, 0, dm, dcells, dtable, dtok, a, b, out,
+                       n, nullptr);
   if (hipDeviceSynchronize() != hipSuccess) return -5;
   hipFree(dm);
   if (dcells) hipFree(dcells);
   if (dtable) hipFree(dtable);
   if (dtok) hipFree(dtok);
   return 0;
-}
 }
