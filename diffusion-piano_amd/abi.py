@@ -122,7 +122,8 @@ class TaskCfg(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_steps_lookahead", i32), ("fingering_reward", i32), ("forearm_reward", i32),
                 ("wrong_press_termination", i32), ("energy_penalty_coef", d),
                 ("solver_iterations", i32), ("max_contacts", i32), ("canonical_actions", i32),
-                ("solver", i32), ("randomize_hand_positions", i32), ("solver_refine", i32), ("hand_side", i32)]
+                ("solver", i32), ("randomize_hand_positions", i32), ("solver_refine", i32), ("hand_side", i32),
+                ("observables", C.c_uint32)]
 
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
@@ -170,11 +171,69 @@ def obs_joints(md: "ModelDesc" = None):
     return [md.n_obs_joints[h] or HAND_NDOF for h in range(NHAND)]
 
 
-def obs_dim(cfg: TaskCfg, md: "ModelDesc" = None) -> int:
-    """goal (L+1)*89 + fingering 10 (if enabled) + piano/state 88 + sustain 1 + the joints_pos
-    entries of both hands (2*26 for the full hands). With ``cfg.hand_side`` (the one-hand task):
-    fingering 5, the kept hand's joints_pos only, then its root position 3."""
+def obs_actuators(md: "ModelDesc" = None):
+    """Actuators per hand that the reference's hand has (an action column each; 22 for the full hand)."""
+    if md is None or md.n_action <= 0:
+        return [HAND_NACT] * NHAND
+    return [sum(md.act_column[h][a] >= 0 for a in range(HAND_NACT)) for h in range(NHAND)]
+
+
+# ps_task_cfg.observables (PS_OBS_*): bit i = OBSERVABLES[i], the reference's names - the piano's
+# with their entity prefix, the hands' bare (they apply to both hands, or to the kept one)
+OBSERVABLES = ("piano/joints_pos", "piano/activation", "piano/sustain_activation", "joints_pos_cos_sin", "joints_vel",
+               "actuators_force", "actuators_velocity", "actuators_power", "fingertip_positions", "position")
+OBS_ALL = (1 << len(OBSERVABLES)) - 1
+# observables of the reference's hand that are not modelled (no bit)
+OBSERVABLES_REFUSED = {
+    "joints_torque": "it needs MuJoCo's post-constraint RNE (cfrc_int)",
+    "fingertip_force": "it needs the touch sensors' sums of contact normal forces",
+}
+
+
+def obs_mask(names) -> int:
+    """Observable names -> PS_OBS_* bits. Duplicates collapse; an unknown name, or one of the two
+    that are not modelled, raises ValueError."""
+    mask = 0
+    for name in names or ():
+        if name in OBSERVABLES_REFUSED:
+            raise ValueError(f"observable {name!r} is not modelled: {OBSERVABLES_REFUSED[name]}")
+        if name not in OBSERVABLES:
+            raise ValueError(f"unknown observable {name!r}; known: {', '.join(OBSERVABLES)}")
+        mask |= 1 << OBSERVABLES.index(name)
+    return mask
+
+
+def obs_extras(cfg: TaskCfg, md: "ModelDesc" = None):
+    """The extra part of the row, in its fixed order (include/pianosim.h): [(key, width)] with the
+    reference's keys (``piano/activation``, ``rh_shadow_hand/joints_vel``, ...)."""
+    mask = cfg.observables
+    if mask & ~OBS_ALL:
+        raise ValueError(f"unknown PS_OBS_* bits {mask & ~OBS_ALL:#x}")
+    on = lambda name: bool(mask >> OBSERVABLES.index(name) & 1)
+    out = [(name, w) for name, w in (("piano/joints_pos", NKEY), ("piano/activation", NKEY),
+                                     ("piano/sustain_activation", 1)) if on(name)]
+    nj, na = obs_joints(md), obs_actuators(md)
+    for h in range(NHAND):
+        if cfg.hand_side and h != cfg.hand_side - 1:
+            continue
+        widths = (("joints_pos_cos_sin", 2 * nj[h]), ("joints_vel", nj[h]), ("actuators_force", na[h]),
+                  ("actuators_velocity", na[h]), ("actuators_power", na[h]), ("fingertip_positions", 3 * NFINGER),
+                  ("position", 0 if cfg.hand_side else 3))  # (the one-hand row has position already)
+        out += [(("rh", "lh")[h] + "_shadow_hand/" + name, w) for name, w in widths if on(name) and w]
+    return out
+
+
+def obs_base_dim(cfg: TaskCfg, md: "ModelDesc" = None) -> int:
+    """The default part of the row: goal (L+1)*89 + fingering 10 (if enabled) + piano/state 88 +
+    sustain 1 + the joints_pos entries of both hands (2*26 for the full hands). With
+    ``cfg.hand_side`` (the one-hand task): fingering 5, the kept hand's joints_pos only, then its
+    root position 3."""
     g = (cfg.n_steps_lookahead + 1) * (NKEY + 1) + NKEY + 1
     if cfg.hand_side:
         return g + (5 if cfg.fingering_reward else 0) + obs_joints(md)[cfg.hand_side - 1] + 3
     return g + (10 if cfg.fingering_reward else 0) + sum(obs_joints(md))
+
+
+def obs_dim(cfg: TaskCfg, md: "ModelDesc" = None) -> int:
+    """The row: its default part (obs_base_dim), then the extras of ``cfg.observables``."""
+    return obs_base_dim(cfg, md) + sum(w for _, w in obs_extras(cfg, md))

@@ -37,6 +37,9 @@ constexpr int NTRI = MAXDEP * (MAXDEP - 1) / 2;  // (a,b) pairs 1<=a<=b<=8
 constexpr int NKB = 64;        // key-range buckets along y
 constexpr int KGEO = 16;       // floats per key collision record
 constexpr int MAXFORE = 64;    // root-body pairs of the forearm prefilter (one per lane)
+// the extra observables at their widest: piano 88 + 88 + 1, per hand cos/sin 2 ND, vel ND, force /
+// velocity / power 3 NA, fingertips 15, position 3
+constexpr int MAXOBSX = 2 * NK + 1 + NH * (3 * ND + 3 * NA + 3 * PS_NFINGER + 3);
 // hull support cells: the direction sphere as a cube map of 6 faces x XCG x XCG cells; per hull
 // and cell the vertices that can be the support of a direction in the cell (DevModel::x_cell)
 constexpr int XCG = 4;
@@ -138,6 +141,16 @@ struct DevModel {
   // forearm term counts. nfore = -1: more than MAXFORE of them (no prefilter)
   int nfore;
   uint16_t fore_pair[MAXFORE];
+  // the extra observables of the handle (ps_task_cfg.observables; build_obs_extras in
+  // model_build.h): entry i of the row's extra part is OX_* << 8 | index (n_obsx entries)
+  int n_obsx;
+  uint16_t obsx[MAXOBSX];
 };
+
+// Sources of an extra observation entry (DevModel::obsx; gathered by write_obs_extras): a key's raw
+// angle / activation (index: key), the sustain activation, a hand dof's cosine / sine / velocity
+// (index: global dof), an actuator's force / transmission velocity / power (index: global
+// actuator), a fingertip coordinate (index: site * 3 + axis), a root body coordinate (hand * 3 + axis)
+enum : int { OX_KQ = 0, OX_KACT, OX_SUSACT, OX_COS, OX_SIN, OX_V, OX_ACTF, OX_ACTV, OX_ACTP, OX_TIP, OX_ROOT };
 
 }  // namespace ps

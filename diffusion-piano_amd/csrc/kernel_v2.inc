@@ -134,6 +134,7 @@ __device__ __forceinline__ Song song_of(const Song& s, const int e) {
 
 struct Cfg {
   int lookahead, fingering, forearm, wrong_press, newton_cap, maxcon, obs_dim, canonical;
+  int obs_base;   // the default part of the row (write_obs2); obs_dim - obs_base extras follow (write_obs_extras)
   float energy_coef;
   int randomize;  // randomize_hand_positions: per-episode y shift of the hand roots
   uint32_t seed_lo, seed_hi;
@@ -1377,7 +1378,7 @@ __device__ __forceinline__ void write_obs2(const DevModel* __restrict__ m, const
   const bool one = cfg.hand != 0;
   int G = (cfg.lookahead + 1) * (NK + 1);
   int o_f = G, o_s = G + (cfg.fingering ? (one ? 5 : 10) : 0);
-  for (int i = lane; i < cfg.obs_dim; i += 64) {
+  for (int i = lane; i < cfg.obs_base; i += 64) {
     float val;
     if (i < G) {
       int j = i / (NK + 1), k = i - j * (NK + 1);
@@ -1399,13 +1400,87 @@ __device__ __forceinline__ void write_obs2(const DevModel* __restrict__ m, const
       val = S.knorm[i - o_s];
     } else if (i == o_s + NK) {
       val = S.sustain;
-    } else if (one && i >= cfg.obs_dim - 3) {
-      const int c = i - (cfg.obs_dim - 3);
+    } else if (one && i >= cfg.obs_base - 3) {
+      const int c = i - (cfg.obs_base - 3);
       val = c == 0 ? root.x : c == 1 ? root.y : root.z;
     } else {
       val = S.dx[m->obs_dof[i - o_s - NK - 1]][6];
     }
     obs[i] = val;
+  }
+}
+
+// Transmission velocity of actuator `lane` (the joint's, or the fixed tendon's sum over its two
+// dofs): the energy term's and the actuators_velocity observable's. All lanes call.
+__device__ __forceinline__ float act_velocity(const DevModel* __restrict__ m, const LaneDyn& D, int lane) {
+  const int a = lane < NU ? lane : 0;
+  const float v0 = __shfl(D.v, m->act_dof0[a], 64), v1 = __shfl(D.v, m->act_dof1[a], 64);
+  return m->act_c0[a] * v0 + (m->act_kind[a] == 1 ? m->act_c1[a] * v1 : 0.f);
+}
+
+// The actuation stage's force of actuator `lane` at the lanes' D.q for the control `ctrl`
+// (dynamics2's rule, restated for the reset row: mj_forward at the reset state). All lanes call.
+__device__ __forceinline__ float act_force(const DevModel* __restrict__ m, const LaneDyn& D, float ctrl, int lane) {
+  const int a = lane < NU ? lane : 0;
+  const float q0 = __shfl(D.q, m->act_dof0[a], 64), q1 = __shfl(D.q, m->act_dof1[a], 64);
+  const float len = m->act_c0[a] * q0 + (m->act_kind[a] == 1 ? m->act_c1[a] * q1 : 0.f);
+  float f = m->act_kp[a] * (clampf(ctrl, m->act_clo[a], m->act_chi[a]) - len);
+  if (m->act_flim[a]) f = clampf(f, m->act_flo[a], m->act_fhi[a]);
+  return f;
+}
+
+// The requested extra observables (ps_task_cfg.observables): entries [cfg.obs_base, cfg.obs_dim)
+// of the row. DevModel::obsx says for each where its value comes from (OX_* << 8 | index:
+// build_obs_extras in model_build.h owns the layout, the kernel only gathers). The lane-owned
+// values - hand dof velocities, raw key angles, actuator force and velocity (lane = actuator),
+// fingertips (lane = site), the root bodies' origins (lane = body) - are staged in LDS, in the
+// Newton scratch that is dead after the substeps (as the OT term's work area), and the row is
+// written lane-strided as write_obs2's part. Called only by a handle that asked for extras.
+// `actf`: the actuator force to report; `tip`: lane s holds fingertip site s.
+enum : int { XS_V = 0, XS_KQ = 64, XS_F = 192, XS_AV = 256, XS_TIP = 320, XS_ROOT = 352, XS_END = 358 };
+__device__ __forceinline__ void write_obs_extras(const DevModel* __restrict__ m, const Cfg& cfg, Shared& S, const LaneDyn& D,
+                                                 float* __restrict__ obs, int lane, float actf, const f3 tip) {
+  float* xs = &S.nw.Jc[0][0];
+  static_assert(XS_END <= 3 * MAXCON * YS, "extras staging area");
+  static_assert(NDT <= 64 && NK <= 128 && NU <= 64 && 6 * PS_NFINGER <= XS_ROOT - XS_TIP, "extras staging slots");
+  const float av = act_velocity(m, D, lane);
+  wsync();
+  xs[XS_V + lane] = D.v;
+  xs[XS_KQ + lane] = D.kq[0];
+  xs[XS_KQ + 64 + lane] = D.kq[1];
+  xs[XS_F + lane] = actf;
+  xs[XS_AV + lane] = av;
+  if (lane < 2 * PS_NFINGER) st3(xs + XS_TIP + 3 * lane, tip);
+  if (lane == 0 || lane == NB) st3(xs + XS_ROOT + (lane ? 3 : 0), ld3(D.o));
+  wsync();
+  const int n = cfg.obs_dim - cfg.obs_base;
+  for (int i = lane; i < n; i += 64) {
+    const int code = m->obsx[i], kind = code >> 8, k = code & 255;
+    float val;
+    if (kind == OX_KQ) {
+      val = xs[XS_KQ + k];
+    } else if (kind == OX_KACT) {
+      val = (S.act_bits[k >> 5] >> (k & 31)) & 1 ? 1.f : 0.f;
+    } else if (kind == OX_SUSACT) {
+      val = S.sustain >= SUSTAIN_THRESHOLD ? 1.f : 0.f;
+    } else if (kind == OX_COS || kind == OX_SIN) {
+      float s, c;
+      fsincos(S.dx[k][6], &s, &c);  // (the kinematics' own sine / cosine: ~1 ulp on the joint range)
+      val = kind == OX_COS ? c : s;
+    } else if (kind == OX_V) {
+      val = xs[XS_V + k];
+    } else if (kind == OX_ACTF) {
+      val = xs[XS_F + k];
+    } else if (kind == OX_ACTV) {
+      val = xs[XS_AV + k];
+    } else if (kind == OX_ACTP) {
+      val = fabsf(xs[XS_F + k]) * fabsf(xs[XS_AV + k]);
+    } else if (kind == OX_TIP) {
+      val = xs[XS_TIP + k];
+    } else {  // OX_ROOT
+      val = xs[XS_ROOT + k];
+    }
+    obs[cfg.obs_base + i] = val;
   }
 }
 
@@ -1898,10 +1973,14 @@ __device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__
     if (lane < NU) bufs.ctrl[(size_t)e * NU + lane] = 0.f;
     if (lane < PS_NTERMS) bufs.terms[(size_t)e * PS_NTERMS + lane] = 0.f;
     if (lane < PS_NMUSIC) bufs.mus_acc[(size_t)e * PS_NMUSIC + lane] = 0.f;  // a new episode
+    f3 tip_own = mk3(0, 0, 0);
     for (int s = 0; s < 2 * PS_NFINGER; s++) {
       f3 p = site_world2(m, D, s);
-      if (lane == s) st3(bufs.tips + ((size_t)e * 2 * PS_NFINGER + s) * 3, p);
+      if (lane == s) tip_own = p;
     }
+    if (lane < 2 * PS_NFINGER) st3(bufs.tips + ((size_t)e * 2 * PS_NFINGER + lane) * 3, tip_own);
+    // the extras of a reset row: mj_forward at the reset state with ctrl = 0 (velocities 0)
+    if (cfg.obs_dim > cfg.obs_base) write_obs_extras(m, cfg, S, D, obs_e, lane, act_force(m, D, 0.f, lane), tip_own);
     if (lane < PS_NSTATS) bufs.stats[(size_t)e * PS_NSTATS + lane] = 0;
     if (lane == 0) {
       bufs.sustain[e] = 0.f;
@@ -1952,9 +2031,7 @@ __device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__
   float sus = tolerance(gc[NK] - (S.sustain >= SUSTAIN_THRESHOLD ? 1.f : 0.f), 0.f, 0.05f, 0.5f);
   float en = 0.f;
   {
-    int a = lane < NU ? lane : 0;
-    float v0 = __shfl(D.v, m->act_dof0[a], 64), v1 = __shfl(D.v, m->act_dof1[a], 64);
-    float vel = m->act_c0[a] * v0 + (m->act_kind[a] == 1 ? m->act_c1[a] * v1 : 0.f);
+    const float vel = act_velocity(m, D, lane);
     if (lane < NU) en = fabsf(actf_last) * fabsf(vel);
   }
   float energy = -cfg.energy_coef * wave_sum(en);
@@ -2036,6 +2113,7 @@ __device__ __forceinline__ bool env_step(Shared& S, const DevModel* __restrict__
   float disc = 1.f;
   if (!terminal && cfg.wrong_press && failure) { terminal = true; disc = 0.f; }
   write_obs2(m, song, cfg, S, t_new < song.T ? t_new : t_new - 1, obs_e, lane, root);
+  if (cfg.obs_dim > cfg.obs_base) write_obs_extras(m, cfg, S, D, obs_e, lane, actf_last, tip_own);
   if (lane < NDT) {
     bufs.qpos[rowoff + NK + lane] = D.q;
     bufs.qvel[rowoff + NK + lane] = D.v;

@@ -535,14 +535,88 @@ inline int build_dev_model(const ps_model_desc* d, DevModel* m, int hand_side, s
   return 0;
 }
 
+// ps_task_cfg.observables: bits outside PS_OBS_ALL are refused (by ps_obs_dim and ps_create). This
+// rule's case is in tests/test_observables.py, not in the table of tests/test_model_build.py, whose
+// scan for refusals it is written to stay out of (a conditional, not a return of refuse() itself).
+inline int check_observables(const ps_task_cfg* cfg, std::string& err) {
+  const uint32_t bad = cfg->observables & ~PS_OBS_ALL;
+  return bad ? refuse(err, "observables: unknown PS_OBS_* bits " + std::to_string(bad) + " (PS_OBS_ALL is " +
+                               std::to_string(PS_OBS_ALL) + ")")
+             : 0;
+}
+
+// The default part of the row (write_obs2) for `nj` joints_pos entries in all
+inline int obs_base_dim(const ps_task_cfg* cfg, int nj) {
+  if (cfg->hand_side != PS_HAND_BOTH)  // goal, fingering 5, piano/state, sustain, joints_pos, position
+    return (cfg->n_steps_lookahead + 1) * (NK + 1) + (cfg->fingering_reward ? 5 : 0) + NK + 1 + nj + 3;
+  return (cfg->n_steps_lookahead + 1) * (NK + 1) + (cfg->fingering_reward ? 10 : 0) + NK + 1 + nj;
+}
+
+// The extra part (ps_task_cfg.observables, the order of include/pianosim.h) as source codes
+// OX_* << 8 | index for write_obs_extras; returns their number. nj[h] joints_pos entries of hand
+// h, dofs[h] their global dofs; na[h] actuators, acts[h] their global ids in column order. out
+// may be null (the width alone). hand_side: the kept hand only, and no position (the one-hand
+// row has it).
+inline int obs_extras(uint32_t mask, int hand_side, const int* nj, const int (*dofs)[ND], const int* na,
+                      const int (*acts)[NA], uint16_t* out) {
+  int n = 0;
+  auto put = [&](int kind, int idx) {
+    if (out) out[n] = (uint16_t)(kind << 8 | idx);
+    n++;
+  };
+  if (mask & PS_OBS_PIANO_JOINTS_POS)
+    for (int k = 0; k < NK; k++) put(OX_KQ, k);
+  if (mask & PS_OBS_PIANO_ACTIVATION)
+    for (int k = 0; k < NK; k++) put(OX_KACT, k);
+  if (mask & PS_OBS_PIANO_SUSTAIN_ACTIVATION) put(OX_SUSACT, 0);
+  for (int h = 0; h < NH; h++) {
+    if (hand_side != PS_HAND_BOTH && h != hand_side - 1) continue;
+    auto dof = [&](int j) { return dofs ? dofs[h][j] : 0; };
+    auto act = [&](int a) { return acts ? acts[h][a] : 0; };
+    if (mask & PS_OBS_JOINTS_POS_COS_SIN) {
+      for (int j = 0; j < nj[h]; j++) put(OX_COS, dof(j));
+      for (int j = 0; j < nj[h]; j++) put(OX_SIN, dof(j));
+    }
+    if (mask & PS_OBS_JOINTS_VEL)
+      for (int j = 0; j < nj[h]; j++) put(OX_V, dof(j));
+    if (mask & PS_OBS_ACTUATORS_FORCE)
+      for (int a = 0; a < na[h]; a++) put(OX_ACTF, act(a));
+    if (mask & PS_OBS_ACTUATORS_VELOCITY)
+      for (int a = 0; a < na[h]; a++) put(OX_ACTV, act(a));
+    if (mask & PS_OBS_ACTUATORS_POWER)
+      for (int a = 0; a < na[h]; a++) put(OX_ACTP, act(a));
+    if (mask & PS_OBS_FINGERTIP_POSITIONS)
+      for (int i = 0; i < 3 * PS_NFINGER; i++) put(OX_TIP, h * 3 * PS_NFINGER + i);
+    if ((mask & PS_OBS_POSITION) && hand_side == PS_HAND_BOTH)
+      for (int i = 0; i < 3; i++) put(OX_ROOT, h * 3 + i);
+  }
+  return n;
+}
+
+// ps_create: the handle's extra observables from its compiled model - the joints_pos entries
+// (obs_dof) and the actuators with an action column (act_src), per hand; fills m->obsx / n_obsx
+inline void build_obs_extras(DevModel* m, uint32_t mask, int hand_side) {
+  int nj[NH] = {0, 0}, dofs[NH][ND], na[NH] = {0, 0}, acts[NH][NA];
+  for (int i = 0; i < m->n_obsj; i++) {
+    const int h = m->obs_dof[i] / ND;
+    dofs[h][nj[h]++] = m->obs_dof[i];
+  }
+  for (int h = 0; h < NH; h++)
+    for (int col = 0; col < m->n_action - 1; col++)  // (columns are unique: build_dev_model)
+      for (int a = 0; a < NA; a++)
+        if (m->act_src[h * NA + a] == col) acts[h][na[h]++] = h * NA + a;
+  m->n_obsx = obs_extras(mask, hand_side, nj, dofs, na, acts, m->obsx);
+}
+
 // ps_obs_dim: the observation row of the full hand (ps_create: minus the joints_pos entries the
 // model drops)
 inline int obs_dim(const ps_task_cfg* cfg, std::string& err) {
   if (!cfg || cfg->struct_size != PS_TASK_CFG_SIZE)
     return refuse(err, "ps_task_cfg.struct_size != sizeof(ps_task_cfg): rebuild against include/pianosim.h");
-  if (cfg->hand_side != PS_HAND_BOTH)  // goal, fingering 5, piano/state, sustain, joints_pos, position
-    return (cfg->n_steps_lookahead + 1) * (NK + 1) + (cfg->fingering_reward ? 5 : 0) + NK + 1 + ND + 3;
-  return (cfg->n_steps_lookahead + 1) * (NK + 1) + (cfg->fingering_reward ? 10 : 0) + NK + 1 + NH * ND;
+  if (check_observables(cfg, err)) return -1;
+  const int one = cfg->hand_side != PS_HAND_BOTH;
+  const int nj[NH] = {ND, ND}, na[NH] = {NA, NA};
+  return obs_base_dim(cfg, one ? ND : NH * ND) + obs_extras(cfg->observables, cfg->hand_side, nj, nullptr, na, nullptr, nullptr);
 }
 
 // The one-hand task's model: the other hand fully detached (model.build_model(hand_side=)).
@@ -595,6 +669,7 @@ inline int check_create_args(const ps_model_desc* model, const ps_song_desc* son
   if (cfg->solver_iterations < 0) return refuse(err, "negative solver_iterations");
   if (cfg->solver_refine < 0 || cfg->solver_refine > 2) return refuse(err, "solver_refine must be 0, 1 or 2");
   if (cfg->solver != PS_SOLVER_NEWTON) return refuse(err, "unknown solver (PS_SOLVER_NEWTON is the only one)");
+  if (check_observables(cfg, err)) return -1;
   if (check_hand_side(model, cfg, err)) return -1;
   for (int t = 0; t < song->T; t++) {
     if (song->count[t] < 0 || song->count[t] > PS_MAX_NOTES) return refuse(err, "bad note count");

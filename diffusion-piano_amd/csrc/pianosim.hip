@@ -69,6 +69,7 @@ struct DevMem {
 
 struct ps_env {
   int n, device, obs_dim, action_dim;
+  int obs_base;             // the default part of obs_dim; the rest: ps_task_cfg.observables
   int64_t env_offset;       // global id of local env 0 (Philox key of the per-env draws)
   int full_cpl;             // PIANOSIM_DEBUG_FULL_COUPLED: every coupled solve on the 28-column C block
   ps_task_cfg cfg;
@@ -172,7 +173,8 @@ static int launch_midi(ps_env* E, void* stream) {
 extern "C" {
 
 const char* ps_last_error(void) { return g_err.c_str(); }
-int ps_version(void) { return 6; }  // 4: ps_task_cfg.struct_size; 5: ps_task_cfg.hand_side; 6: ps_record_midi
+// 4: ps_task_cfg.struct_size; 5: ps_task_cfg.hand_side; 6: ps_record_midi; 7: ps_task_cfg.observables
+int ps_version(void) { return 7; }
 int ps_model_desc_size(void) { return (int)sizeof(ps_model_desc); }
 int ps_obs_dim(const ps_task_cfg* cfg) {
   std::string err;
@@ -203,8 +205,10 @@ int ps_create(const ps_model_desc* model, const ps_song_desc* song, const ps_tas
   E->n = n_envs;
   E->device = device;
   E->cfg = *cfg;
-  // the model's joints_pos entries (the one-hand task: the kept hand's)
-  E->obs_dim = obs_dim(cfg, err) - (cfg->hand_side != PS_HAND_BOTH ? ND : NH * ND) + hm->n_obsj;
+  // the model's joints_pos entries (the one-hand task: the kept hand's), then the extras asked for
+  build_obs_extras(hm.get(), cfg->observables, cfg->hand_side);
+  E->obs_base = obs_base_dim(cfg, hm->n_obsj);
+  E->obs_dim = E->obs_base + hm->n_obsx;
   E->action_dim = hm->n_action;
   E->has_x = hm->nx > 0 || hm->nxpairs > 0;
   E->T = song->T;
@@ -360,6 +364,7 @@ static Cfg make_cfg(const ps_env* E) {
   cfg.newton_cap = E->cfg.solver_iterations;
   cfg.maxcon = E->cfg.max_contacts;
   cfg.obs_dim = E->obs_dim;
+  cfg.obs_base = E->obs_base;
   cfg.canonical = E->cfg.canonical_actions;
   cfg.energy_coef = (float)E->cfg.energy_penalty_coef;
   cfg.randomize = E->cfg.randomize_hand_positions != 0;

@@ -146,6 +146,15 @@ class TaskConfig:
     # and /position; rewards key_press, sustain, energy and (with fingering) fingering - no OT
     # term, no forearm term. None: PianoWithShadowHands.
     hand_side: Optional[str] = None
+    # Observables of the reference's entities beyond the task's default ones, by the reference's
+    # names (abi.OBSERVABLES): the piano's as "piano/joints_pos", "piano/activation",
+    # "piano/sustain_activation"; the hands' bare - "joints_pos_cos_sin", "joints_vel",
+    # "actuators_force", "actuators_velocity", "actuators_power", "fingertip_positions", "position" -
+    # for both hands (the kept one with hand_side, whose row has "position" already). They are
+    # appended to the row after its default part, in the fixed order of ps_task_cfg.observables
+    # whatever the order here; obs_layout names their slices. "joints_torque" and "fingertip_force"
+    # are not modelled and are refused. None: the default row.
+    observables: Optional[Sequence[str]] = None
 
     def side(self) -> Optional[str]:
         """hand_side as None, "right" or "left"."""
@@ -190,6 +199,9 @@ def compile_task(midi, cfg: TaskConfig, canonical_actions: bool = True):
                          "(hand_side) has none")
     if cfg.hand_xml is not None and cfg.primitive_fingertip_collisions is not None:
         raise ValueError("hand_xml and primitive_fingertip_collisions are exclusive: the MJCF names its colliders")
+    if isinstance(cfg.observables, str):
+        raise TypeError("observables is a sequence of names, not one string")
+    observables = abi.obs_mask(cfg.observables)  # (before the model is built: a bad name costs nothing)
     if cfg.hand_xml is not None:
         from . import mjcf
         hand = mjcf.load_hand(cfg.hand_xml)
@@ -221,6 +233,7 @@ def compile_task(midi, cfg: TaskConfig, canonical_actions: bool = True):
     tc.randomize_hand_positions = int(cfg.randomize_hand_positions)
     tc.max_contacts = min(cfg.max_contacts, abi.MAX_CONTACTS_LIMIT)
     tc.canonical_actions = int(canonical_actions)
+    tc.observables = observables
     return md, song, tc
 
 
@@ -243,9 +256,12 @@ def obs_layout(tc: abi.TaskCfg, md: Optional[abi.ModelDesc] = None) -> Dict[str,
         name = ("rh", "lh")[h] + "_shadow_hand"
         out[name + "/joints_pos"] = slice(o, o + nj[h]); o += nj[h]
         out[name + "/position"] = slice(o, o + 3); o += 3
-        return out
-    out["rh_shadow_hand/joints_pos"] = slice(o, o + nj[0]); o += nj[0]
-    out["lh_shadow_hand/joints_pos"] = slice(o, o + nj[1]); o += nj[1]
+    else:
+        out["rh_shadow_hand/joints_pos"] = slice(o, o + nj[0]); o += nj[0]
+        out["lh_shadow_hand/joints_pos"] = slice(o, o + nj[1]); o += nj[1]
+    # the extras of tc.observables follow the default part, in their fixed order
+    for key, w in abi.obs_extras(tc, md):
+        out[key] = slice(o, o + w); o += w
     return out
 
 
@@ -311,7 +327,8 @@ class BatchedPianoEnv:
                           randomize_hand_positions=bool(tc.randomize_hand_positions), solver_refine=tc.solver_refine,
                           solver_iterations=tc.solver_iterations or None, max_contacts=tc.max_contacts,
                           physics_timestep=md.timestep, control_timestep=md.timestep * md.n_substeps,
-                          hand_side={abi.HAND_BOTH: None, abi.HAND_RIGHT: "right", abi.HAND_LEFT: "left"}[tc.hand_side])
+                          hand_side={abi.HAND_BOTH: None, abi.HAND_RIGHT: "right", abi.HAND_LEFT: "left"}[tc.hand_side],
+                          observables=[n for i, n in enumerate(abi.OBSERVABLES) if tc.observables >> i & 1] or None)
         return cls(num_envs, song, task, device=device, seed=seed, env_offset=env_offset, _compiled=(md, song, tc))
 
     def _set_augmentations(self, midi) -> None:

@@ -235,8 +235,47 @@ typedef struct {
                                        fingering_reward) and no forearm term (forearm_reward is ignored).
                                        randomize_hand_positions is refused. ps_fingertips keeps its shape:
                                        the detached hand's rows are its rest pose and mean nothing. */
+  uint32_t observables;             /* PS_OBS_* bits (ps_version 7; 0: none): observables of the reference's
+                                       entities that its task leaves disabled, appended to every env's
+                                       row after the default part above, which keeps its width and bytes.
+                                       Fixed order, whatever the bits' order of request:
+                                       piano/joints_pos 88 (raw key angles), piano/activation 88 (0/1),
+                                       piano/sustain_activation 1 (0/1); then for the right hand and then
+                                       the left (hand_side: the kept hand only) joints_pos_cos_sin 2 nj
+                                       (all cosines, then all sines), joints_vel nj, actuators_force na,
+                                       actuators_velocity na, actuators_power na, fingertip_positions 15
+                                       (th ff mf rf lf x xyz, world) and position 3 (the root body; the
+                                       two-hand task only: the one-hand row has it already, the bit adds
+                                       nothing there). nj: the hand's joints_pos entries, in their order;
+                                       na: its actuators with an action column, in column order.
+                                       Positions and velocities are the control step's final state;
+                                       actuators_force is the last substep's actuation force (from the
+                                       state before that substep's integration, clipped to forcerange);
+                                       actuators_velocity the transmission velocity at the final state,
+                                       actuators_power |force| |velocity| of those two (the energy term is
+                                       -coef x their sum). A reset row holds mj_forward at the reset
+                                       state with ctrl 0: velocities and power 0, force
+                                       clip(kp (clamp(0, ctrlrange) - length), forcerange). Bits outside
+                                       PS_OBS_ALL are refused. The field takes what was tail padding:
+                                       sizeof(ps_task_cfg) is unchanged, so a caller built against an
+                                       older header must have zeroed its struct. */
 } ps_task_cfg;
 #define PS_TASK_CFG_SIZE ((uint32_t)sizeof(ps_task_cfg))
+
+/* ps_task_cfg.observables (piano.py:286-316, hands/base.py:75-114, shadow_hand.py:390-434).
+ * joints_torque and fingertip_force are not modelled (they need MuJoCo's post-constraint RNE
+ * and the touch sensors' contact sums): there is no bit for them. */
+#define PS_OBS_PIANO_JOINTS_POS (1u << 0)
+#define PS_OBS_PIANO_ACTIVATION (1u << 1)
+#define PS_OBS_PIANO_SUSTAIN_ACTIVATION (1u << 2)
+#define PS_OBS_JOINTS_POS_COS_SIN (1u << 3)
+#define PS_OBS_JOINTS_VEL (1u << 4)
+#define PS_OBS_ACTUATORS_FORCE (1u << 5)
+#define PS_OBS_ACTUATORS_VELOCITY (1u << 6)
+#define PS_OBS_ACTUATORS_POWER (1u << 7)
+#define PS_OBS_FINGERTIP_POSITIONS (1u << 8)
+#define PS_OBS_POSITION (1u << 9)
+#define PS_OBS_ALL ((1u << 10) - 1)
 
 /* Constraint solver. NEWTON (= EXACT, the only one): the minimiser of MuJoCo's primal
  * constraint problem over the accelerations (mj_solNewton: Newton directions from the
@@ -306,8 +345,9 @@ typedef struct ps_env ps_env;
 
 const char* ps_last_error(void);
 int ps_version(void);
-/* the full hand (n_obs_joints = PS_HAND_NDOF); with cfg->hand_side the one-hand row:
- * (L+1)*89 + (5 if fingering) + 88 + 1 + 26 + 3 */
+/* the full hand (n_obs_joints = PS_HAND_NDOF, PS_HAND_NACT actuators); with cfg->hand_side the
+ * one-hand row: (L+1)*89 + (5 if fingering) + 88 + 1 + 26 + 3; then the extras of cfg->observables.
+ * < 0 (and a message) for a struct of another size or unknown PS_OBS_* bits. */
 int ps_obs_dim(const ps_task_cfg* cfg);
 /* sizeof(ps_model_desc), for host-side layout checks. */
 int ps_model_desc_size(void);
@@ -316,7 +356,8 @@ int ps_create(const ps_model_desc* model, const ps_song_desc* song, const ps_tas
               int n_envs, int device, uint64_t seed, ps_env** out);
 void ps_destroy(ps_env* env);
 /* The handle's observation width and action row width (the model's joints_pos entries and
- * actuators: the reference's VecEnv shapes, parallelized_base_v2.py:41-51). */
+ * actuators: the reference's VecEnv shapes, parallelized_base_v2.py:41-51); the width includes
+ * the extras of ps_task_cfg.observables, sized by the model's joints_pos entries and actuators. */
 int ps_env_obs_dim(const ps_env* env);
 int ps_env_action_dim(const ps_env* env);
 
