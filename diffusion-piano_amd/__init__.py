@@ -6,9 +6,10 @@ package name required by the build layout).
 
 from . import abi, music, model, mjcf, evaluation, variations  # noqa: F401
 from .envs import (  # noqa: F401
-    Array, BatchedPianoEnv, BoundedArray, DEBUG, Environment, HandSide, PhysicsError, StepType, TaskConfig, TimeStep,
-    VectorizedPianoEnv, compile_task, load, obs_layout,
+    Array, BatchedPianoEnv, BoundedArray, DEBUG, Environment, HandSide, PhysicsError, Snapshot, StepType, TaskConfig,
+    TimeStep, VectorizedPianoEnv, compile_task, load, obs_layout,
 )
 from .evaluation import MidiEvaluationWrapper  # noqa: F401,E402
 from ._lib import PianosimError  # noqa: F401,E402
+from .planning import PredictiveSampler  # noqa: F401,E402
 from .variations import MidiOctaveShift, MidiPitchShift, MidiSelect, MidiTemporalStretch  # noqa: F401,E402

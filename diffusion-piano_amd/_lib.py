@@ -19,13 +19,15 @@ EXPORTS = (
     "ps_set_hand_offset", "ps_record_contacts", "ps_contacts", "ps_set_env_offset", "ps_warnings",
     "ps_env_obs_dim", "ps_env_action_dim", "ps_episode_returns", "ps_set_augmentations", "ps_get_augmentation",
     "ps_set_augmentation", "ps_get_song_tables", "ps_record_midi", "ps_midi_events", "ps_midi_push",
+    "ps_snapshot_create", "ps_snapshot_bytes", "ps_snapshot_save", "ps_snapshot_restore", "ps_snapshot_destroy",
 )
 
 # Every entry point declared in include/pianorl.h.
 RL_EXPORTS = ("prl_last_error", "prl_version", "prl_running_norm", "prl_gae", "prl_normalize", "prl_gauss_sample",
               "prl_clip_adam", "prl_gather_minibatch", "prl_lnrelu_fwd", "prl_lnrelu_bwd", "prl_actor_head",
               "prl_critic_head", "prl_colsums", "prl_mlp_step_work", "prl_mlp_step", "prl_mlp_step_idx",
-              "prl_mlp_step_norm_parts", "prl_mlp_step_idx_norm", "prl_clip_adam_parts")
+              "prl_mlp_step_norm_parts", "prl_mlp_step_idx_norm", "prl_clip_adam_parts", "prl_plan_perturb",
+              "prl_plan_action", "prl_plan_accumulate", "prl_plan_select")
 
 
 class PrlLayer(C.Structure):  # prl_layer of include/pianorl.h
@@ -89,6 +91,14 @@ def load() -> C.CDLL:
         if name not in ("ps_last_error", "ps_version", "ps_model_desc_size", "ps_destroy") and hasattr(L, name):
             getattr(L, name).restype = i32
     L.ps_destroy.restype = None
+    if hasattr(L, "ps_snapshot_create"):
+        L.ps_snapshot_create.argtypes = [vp, u64, C.POINTER(vp)]
+        L.ps_snapshot_bytes.argtypes = [vp]
+        L.ps_snapshot_bytes.restype = u64
+        L.ps_snapshot_save.argtypes = [vp, vp, vp]
+        L.ps_snapshot_restore.argtypes = [vp, vp, vp, vp, vp]
+        L.ps_snapshot_destroy.argtypes = [vp]
+        L.ps_snapshot_destroy.restype = None
     _lib = L
     return L
 
@@ -134,8 +144,14 @@ def load_rl() -> C.CDLL:
                                             vp, vp, vp, C.c_size_t, vp, C.POINTER(C.c_int64), i32, vp, vp, i32, vp, vp]
         L.prl_clip_adam_parts.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int64), i32, vp, vp, f32, f32, f32, f32, vp, i32,
                                           vp, vp]
+    if hasattr(L, "prl_plan_select"):
+        L.prl_plan_perturb.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, u64, u64, vp, vp]
+        L.prl_plan_action.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, vp]
+        L.prl_plan_accumulate.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp, vp]
+        L.prl_plan_select.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     for name in RL_EXPORTS[2:]:
-        getattr(L, name).restype = i32
+        if hasattr(L, name):
+            getattr(L, name).restype = i32
     if hasattr(L, "prl_mlp_step_work"):
         L.prl_mlp_step_work.restype = C.c_size_t
     _rl = L

@@ -543,7 +543,7 @@ __global__ void colsums_final_kernel(ColSums cs, int nchunks) {
 extern "C" {
 
 const char* prl_last_error(void) { return g_err.c_str(); }
-int prl_version(void) { return 2; }  // 2: the guard word of prl_mlp_step* / prl_clip_adam*
+int prl_version(void) { return 3; }  // 2: the guard word of prl_mlp_step* / prl_clip_adam*; 3: prl_plan_*
 
 int prl_running_norm(const float* x, int n, double* stats, float* out, void* stream) {
   if (!x || !stats || !out || n <= 0) return fail("prl_running_norm: null pointer or n <= 0");
@@ -1033,3 +1033,5 @@ int prl_mlp_timing_get(uint64_t* out /* host [2][32] */) {
 #endif
 
 }  // extern "C"
+
+#include "plan.inc"

@@ -122,6 +122,9 @@ struct ps_env {
   // by ps_set_augmentations), con_out (switched by ps_record_contacts), the MIDI recorder's
   // (replaced or freed by ps_record_midi)
   DevMem mem, aug_mem, con_mem, midi_mem;
+  // counts the calls that changed the set of per-env buffers (ps_set_augmentations, ps_record_midi,
+  // ps_record_contacts): a snapshot lists the buffers of one generation (snapshot.inc)
+  uint64_t row_gen;
 };
 
 // Every entry point that touches device memory or launches binds the handle's device for its
@@ -142,6 +145,8 @@ struct DeviceGuard {
 #define GUARD(E)                                                                  \
   DeviceGuard guard_((E)->device);                                                \
   if (!guard_.ok) return fail("hipSetDevice(" + std::to_string((E)->device) + ") failed")
+
+#include "snapshot.inc"
 
 // n elements device to device on the stream; a null caller pointer (dst or src) skips the copy
 template <class T>
@@ -173,8 +178,9 @@ static int launch_midi(ps_env* E, void* stream) {
 extern "C" {
 
 const char* ps_last_error(void) { return g_err.c_str(); }
-// 4: ps_task_cfg.struct_size; 5: ps_task_cfg.hand_side; 6: ps_record_midi; 7: ps_task_cfg.observables
-int ps_version(void) { return 7; }
+// 4: ps_task_cfg.struct_size; 5: ps_task_cfg.hand_side; 6: ps_record_midi; 7: ps_task_cfg.observables;
+// 8: ps_snapshot_*
+int ps_version(void) { return 8; }
 int ps_model_desc_size(void) { return (int)sizeof(ps_model_desc); }
 int ps_obs_dim(const ps_task_cfg* cfg) {
   std::string err;
@@ -619,9 +625,11 @@ int ps_record_contacts(ps_env* E, int on) {
   GUARD(E);
   if (on && !E->con_out) {
     HIPCHK(E->con_mem.alloc(E->con_out, MAXCON * (size_t)E->n, true));
+    E->row_gen++;
   } else if (!on && E->con_out) {
     E->con_mem.clear();
     E->con_out = nullptr;
+    E->row_gen++;
   }
   return 0;
 }
@@ -649,6 +657,7 @@ int ps_set_augmentations(ps_env* E, const ps_augment_desc* d) {
   DevMem& mem = E->aug_mem;
   mem.clear();
   E->aug_on = false;
+  E->row_gen++;
   if (!d) return 0;
   if (d->struct_size != PS_AUGMENT_DESC_SIZE)
     return fail("ps_augment_desc.struct_size != sizeof(ps_augment_desc): rebuild against include/pianosim.h");
@@ -781,6 +790,7 @@ int ps_record_midi(ps_env* E, int max_events, uint64_t max_bytes) {
   E->midi_mem.clear();
   E->keybits = nullptr;
   E->midi = MidiRec{};
+  E->row_gen++;
   if (!max_events) return 0;
   MidiRec r{};
   uint32_t* kbits = nullptr;
@@ -874,6 +884,77 @@ int ps_episode_returns(const float* reward, const uint8_t* step_type, int n, dou
   hipLaunchKernelGGL(episode_returns_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, reward, step_type, n, running,
                      last_return, finished_sum, finished_count);
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ps_snapshot_create(ps_env* E, uint64_t max_bytes, ps_snapshot** out) {
+  if (!E || !out) return fail("null argument");
+  std::unique_ptr<ps_snapshot> S(new ps_snapshot());
+  std::string err;
+  if (snapshot_rows(E, S->table, err)) return fail(err);
+  // every buffer's copy starts 256-byte aligned
+  const size_t N = (size_t)E->n;
+  std::vector<size_t> at(S->table.n);
+  size_t total = 0, per_env = 0;
+  for (int r = 0; r < S->table.n; r++) {
+    at[r] = total;
+    total += (N * S->table.row[r].snap_stride + 255) & ~(size_t)255;
+    per_env += S->table.row[r].snap_stride;
+  }
+  if (max_bytes && total > max_bytes)
+    return fail("ps_snapshot_create: the snapshot needs " + std::to_string(total) + " B (" + std::to_string(E->n) +
+                " envs x " + std::to_string(per_env) + " B in " + std::to_string(S->table.n) +
+                " rows), over the budget of " + std::to_string(max_bytes) + " B");
+  GUARD(E);
+  char* base = nullptr;
+  HIPCHK(S->mem.alloc(base, total, true));
+  HIPCHK(hipDeviceSynchronize());
+  for (int r = 0; r < S->table.n; r++) S->table.row[r].snap = base + at[r];
+  S->owner = E;
+  S->config = E->row_gen;
+  S->bytes = total;
+  S->device = E->device;
+  *out = S.release();
+  return 0;
+}
+
+uint64_t ps_snapshot_bytes(const ps_snapshot* S) { return S ? S->bytes : 0; }
+
+void ps_snapshot_destroy(ps_snapshot* S) {
+  if (!S) return;
+  DeviceGuard guard_(S->device);
+  delete S;  // (its DevMem frees the device memory)
+}
+
+static int snapshot_usable(const ps_env* E, const ps_snapshot* S, const char* what) {
+  if (!E || !S) return fail(std::string(what) + ": null argument");
+  if (S->owner != E) return fail(std::string(what) + ": the snapshot was created on another handle");
+  if (S->config != E->row_gen)
+    return fail(std::string(what) + ": ps_set_augmentations, ps_record_midi or ps_record_contacts changed the "
+                "handle's per-env buffers after the snapshot was created; create a new one");
+  return 0;
+}
+
+int ps_snapshot_save(ps_env* E, ps_snapshot* S, void* stream) {
+  if (snapshot_usable(E, S, "ps_snapshot_save")) return -1;
+  GUARD(E);
+  if (materialise_ncon(E, stream)) return -1;  // (the stored counts are real)
+  hipLaunchKernelGGL((snapshot_copy_kernel<false>), dim3(E->n), dim3(SNAP_THREADS), 0, (hipStream_t)stream, S->table,
+                     (const int*)nullptr, (int*)nullptr, E->n);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ps_snapshot_restore(ps_env* E, const ps_snapshot* S, const int32_t* src, int32_t* n_bad, void* stream) {
+  if (snapshot_usable(E, S, "ps_snapshot_restore")) return -1;
+  GUARD(E);
+  hipLaunchKernelGGL((snapshot_copy_kernel<true>), dim3(E->n), dim3(SNAP_THREADS), 0, (hipStream_t)stream, S->table,
+                     src, n_bad, E->n);
+  HIPCHK(hipGetLastError());
+  // every env has its saved counts again: they are fresh. With src an env may have been left as it
+  // was, so the flag stays; a later pass then recomputes every env's count from its state rows,
+  // which gives the restored envs the counts they were saved with
+  if (!src && !capturing(stream)) E->ncon_stale = false;
   return 0;
 }
 

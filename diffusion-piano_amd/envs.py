@@ -618,6 +618,44 @@ class BatchedPianoEnv:
         return music.sequence_from_messages(music.decode_events(words, count, dt), substeps * dt,
                                             title=f"env {i} ({which})")
 
+    # -- snapshots: save, restore and fork whole envs on the device (ps_snapshot_*)
+    def snapshot(self, max_bytes: int = 0) -> "Snapshot":
+        """A snapshot of every env as it is now: all the handle keeps per env (include/pianosim.h
+        lists it) and the obs / reward / discount / step_type tensors. It belongs to this env and
+        to its configuration now: ``record_midi`` / ``record_contacts`` afterwards invalidate it.
+        ``max_bytes`` (0: no limit) bounds its device memory; more is an error."""
+        return Snapshot(self, max_bytes)
+
+    def restore(self, snap: "Snapshot", src=None) -> None:
+        """Puts the envs back where ``snap`` has them. ``src`` None: every env takes its own row
+        (a replay from here repeats bit for bit). ``src`` [N] int32: env i takes env ``src[i]``'s row
+        - the fork; -1 leaves env i as it is, and so does any other index outside [0, N), which
+        ``snap.n_bad`` (a device int32) counts. Forked envs keep their own ids, so with
+        ``randomize_hand_positions`` or augmentations they draw differently at their next reset.
+        Asynchronous on the current stream."""
+        if not isinstance(snap, Snapshot) or snap._s is None:
+            raise _lib.PianosimError("restore needs an open Snapshot")
+        torch = self._torch
+        sptr = nptr = None
+        if src is not None:
+            s = torch.as_tensor(src, device=self.device).to(torch.int32).contiguous()
+            if s.shape != (self.num_envs,):
+                raise ValueError(f"src must be [{self.num_envs}], got {tuple(s.shape)}")
+            snap._src = s  # keep alive until the kernel ran
+            snap.n_bad.zero_()
+            sptr, nptr = s.data_ptr(), snap.n_bad.data_ptr()
+        _lib.check(_lib.load().ps_snapshot_restore(self._h, snap._s, sptr, nptr, self.stream))
+        # the caller-owned tensors, gathered the same way
+        if src is None:
+            for name, t in snap._outs.items():
+                getattr(self, name).copy_(t)
+            return
+        ok = (s >= 0) & (s < self.num_envs)
+        idx = torch.where(ok, s, torch.zeros_like(s)).long()
+        for name, t in snap._outs.items():
+            cur = getattr(self, name)
+            cur.copy_(torch.where(ok.view(-1, *([1] * (cur.dim() - 1))), t.index_select(0, idx), cur))
+
     def obs_dict(self, obs=None) -> Dict[str, Any]:
         obs = self.obs if obs is None else obs
         return {k: obs[:, s] for k, s in self.obs_slices.items()}
@@ -632,6 +670,47 @@ class BatchedPianoEnv:
             return BoundedArray((n,), np.float32, -np.ones(n, np.float32), np.ones(n, np.float32), "action")
         return BoundedArray((n,), np.float32, self.action_lo.astype(np.float32),
                             self.action_hi.astype(np.float32), "action")
+
+
+class Snapshot:
+    """One saved copy of every env of a :class:`BatchedPianoEnv` (``env.snapshot()``): the
+    library's rows (ps_snapshot_*) and clones of the env's obs / reward / discount / step_type
+    tensors. ``save()`` overwrites it with the envs as they are now; ``env.restore(snap, src)``
+    reads it; ``close()`` frees it (before the env is closed)."""
+
+    def __init__(self, env: BatchedPianoEnv, max_bytes: int = 0):
+        self._env, self._s, self._src = env, None, None
+        s = C.c_void_p()
+        _lib.check(_lib.load().ps_snapshot_create(env._h, int(max_bytes), C.byref(s)))
+        self._s = s
+        self.bytes = int(_lib.load().ps_snapshot_bytes(s))
+        self.n_bad = env._torch.zeros(1, device=env.device, dtype=env._torch.int32)
+        self._outs = {k: env._torch.empty_like(getattr(env, k)) for k in ("obs", "reward", "discount", "step_type")}
+        try:
+            self.save()
+        except Exception:
+            self.close()
+            raise
+
+    def save(self) -> "Snapshot":
+        if self._s is None:
+            raise _lib.PianosimError("the snapshot is closed")
+        env = self._env
+        _lib.check(_lib.load().ps_snapshot_save(env._h, self._s, env.stream))
+        for k, t in self._outs.items():
+            t.copy_(getattr(env, k))
+        return self
+
+    def close(self) -> None:
+        if self._s is not None:
+            _lib.load().ps_snapshot_destroy(self._s)
+            self._s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ---------------------------------------------------------------- reference surfaces

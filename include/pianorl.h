@@ -200,6 +200,38 @@ int prl_mlp_step_idx_norm(const prl_net* nets, const float* S, int sdim, const f
                           float* work, size_t work_floats, const float* grad_base, const int64_t* seg_end, int nseg,
                           float* adam_step, double* norm_part, int nparts, unsigned* guard, void* stream);
 
+/* ---- the predictive-sampling planner's kernels (prl_version 3; planning.py drives them).
+ *
+ * N = G * C candidate envs: group g owns envs [g C, (g + 1) C) and candidate c of it is env
+ * g C + c (candidate 0: the group's leader). A plan is P knots of A actions over a horizon of H
+ * control steps, 1 <= P <= H; knot p sits at step p (H - 1) / (P - 1), a single knot at step 0.
+ * Between knots the plan is the knot at or before the step (PRL_PLAN_ZERO) or the line between
+ * the two around it (PRL_PLAN_LINEAR: the knot itself, bitwise, at a knot's step). */
+#define PRL_PLAN_ZERO 0
+#define PRL_PLAN_LINEAR 1
+#define PRL_STEP_LAST 2 /* ps_step's step_type of an episode's last step (PS_LAST) */
+/* knots [N][P][A] from nominal [G][P][A]: candidate 0 of a group is clamp(nominal, lo, hi), candidate
+ * c >= 1 clamp(nominal + sigma[a] z, lo[a], hi[a]) with z the standard-normal draw of
+ * prl_gauss_sample at column p A + a, row g C + c, the same seed and offset. sigma, lo, hi [A]. */
+int prl_plan_perturb(const float* nominal, const float* sigma, const float* lo, const float* hi, int G, int C, int P,
+                     int A, uint64_t seed, uint64_t offset, float* knots, void* stream);
+/* action [N][A]: every candidate's plan at horizon step h, 0 <= h < H. */
+int prl_plan_action(const float* knots, int N, int P, int A, int H, int h, int interpolation, float* action,
+                    void* stream);
+/* After the ps_step of a horizon step: ret[n] += w[n] reward[n], then w[n] *= gamma discount[n], and
+ * w[n] = 0 when step_type[n] is LAST - what an auto-reset env returns afterwards (the next episode's
+ * FIRST step and its rewards) adds nothing. init != 0 starts from ret = 0, w = 1 (the horizon's
+ * first step). reward, discount, ret, w [N] f32; step_type [N] u8. */
+int prl_plan_accumulate(const float* reward, const float* discount, const uint8_t* step_type, int N, float gamma,
+                        int init, float* ret, float* w, void* stream);
+/* Per group the candidate of the largest ret (ties: the lowest index; a NaN is never chosen unless
+ * all of the group's are NaN, then candidate 0): best [G] i32 (the index in the group), best_ret
+ * [G], the winner's knots as the group's new nominal_out [G][P][A] and its first action chosen
+ * [G][A]. shift != 0: nominal_out is the winner's plan read one control step later at every knot's
+ * step, the last knot held - the warm start of the next plan. One workgroup per group, one launch. */
+int prl_plan_select(const float* ret, const float* knots, int G, int C, int P, int A, int H, int interpolation,
+                    int shift, int32_t* best, float* best_ret, float* nominal_out, float* chosen, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -552,6 +552,47 @@ int ps_midi_events(ps_env* env, int which, uint32_t* events, int32_t* count, int
  * handle's n_substeps. */
 int ps_midi_push(ps_env* env, const uint32_t* bits, int rows, void* stream);
 
+/* ---- snapshots (ps_version 8): save, restore and fork whole envs on the device.
+ *
+ * A snapshot holds one row per env of every per-env device buffer of the handle that a later
+ * step, reset or getter reads: the dynamic state (qpos, qvel, qacc_ws, ctrl, sustain, t_idx,
+ * last), qfrc_applied, the last step's outputs kept for the getters (reward terms, fingertips,
+ * contact counts, solver stats, warnings), the musical-metric accumulators, the hand offset and
+ * the episode counter; on an augmented handle the env's draw and its own song tables; with
+ * contact recording on its contact list; with the MIDI recorder on its two event banks, the
+ * recorder's words and the capture row's header. The step kernels' scratch (the parked lane
+ * state, the queue and the dispatch order) is rewritten by every step before it is read and is
+ * not saved. The caller-owned obs / reward / discount / step_type buffers are the caller's to
+ * keep.
+ *
+ * The rows are listed once, at create time; save and restore walk that one list. A snapshot
+ * belongs to the handle it was created on and to that handle's configuration at the time:
+ * ps_set_augmentations, ps_record_midi or ps_record_contacts after the create change the list,
+ * and save / restore then fail (with a message, launching nothing), as they do on another handle.
+ *
+ * ps_snapshot_create allocates n_envs * (the sum of the row sizes, each rounded up to 16 B)
+ * bytes and fails, with the sizes in the message, when that exceeds max_bytes (0: no limit): an
+ * augmented handle's tables are 488 B per env and row. It saves nothing yet. Init-time.
+ *
+ * ps_snapshot_save first makes the lazy contact counts real (as ps_set_state does), then copies
+ * every row. ps_snapshot_restore is one kernel launch. src == NULL: every env takes its own row.
+ * src [N] (device): env i takes the row of env src[i] - the fork. src[i] == -1 leaves env i as
+ * it is; any other index outside [0, N) leaves it as it is too and adds one to *n_bad (device,
+ * may be NULL; the caller zeroes it). Both are asynchronous on the stream and legal under
+ * stream capture.
+ *
+ * The per-env random draws (randomize_hand_positions, the augmentations) stay keyed by (seed,
+ * global env id, episode). A fork copies the source's episode counter, but the destination keeps
+ * its own id: forks of one env are bitwise copies until their next reset and draw different
+ * hand offsets / augmentations there. That is intended - a fork is another env at the same
+ * state, not a replay; ps_snapshot_restore with src == NULL is the replay. */
+typedef struct ps_snapshot ps_snapshot;
+int ps_snapshot_create(ps_env* env, uint64_t max_bytes, ps_snapshot** out);
+uint64_t ps_snapshot_bytes(const ps_snapshot* snap);
+int ps_snapshot_save(ps_env* env, ps_snapshot* snap, void* stream);
+int ps_snapshot_restore(ps_env* env, const ps_snapshot* snap, const int32_t* src, int32_t* n_bad, void* stream);
+void ps_snapshot_destroy(ps_snapshot* snap);
+
 #ifdef __cplusplus
 }
 #endif
