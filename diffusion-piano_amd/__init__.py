@@ -4,7 +4,7 @@ Import with ``importlib.import_module("diffusion-piano_amd")`` (the directory na
 package name required by the build layout).
 """
 
-from . import abi, music, model, mjcf, evaluation, variations  # noqa: F401
+from . import abi, music, model, mjcf, evaluation, rendering, variations  # noqa: F401
 from .envs import (  # noqa: F401
     Array, BatchedPianoEnv, BoundedArray, DEBUG, Environment, HandSide, PhysicsError, Snapshot, StepType, TaskConfig,
     TimeStep, VectorizedPianoEnv, compile_task, load, obs_layout,
@@ -12,4 +12,5 @@ from .envs import (  # noqa: F401
 from .evaluation import MidiEvaluationWrapper  # noqa: F401,E402
 from ._lib import PianosimError  # noqa: F401,E402
 from .planning import PredictiveSampler  # noqa: F401,E402
+from .rendering import CAMERAS, Camera, PixelWrapper, write_png  # noqa: F401,E402
 from .variations import MidiOctaveShift, MidiPitchShift, MidiSelect, MidiTemporalStretch  # noqa: F401,E402

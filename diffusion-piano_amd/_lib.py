@@ -20,6 +20,7 @@ EXPORTS = (
     "ps_env_obs_dim", "ps_env_action_dim", "ps_episode_returns", "ps_set_augmentations", "ps_get_augmentation",
     "ps_set_augmentation", "ps_get_song_tables", "ps_record_midi", "ps_midi_events", "ps_midi_push",
     "ps_snapshot_create", "ps_snapshot_bytes", "ps_snapshot_save", "ps_snapshot_restore", "ps_snapshot_destroy",
+    "ps_render", "ps_render_list_stats",
 )
 
 # Every entry point declared in include/pianorl.h.
@@ -99,6 +100,9 @@ def load() -> C.CDLL:
         L.ps_snapshot_restore.argtypes = [vp, vp, vp, vp, vp]
         L.ps_snapshot_destroy.argtypes = [vp]
         L.ps_snapshot_destroy.restype = None
+    if hasattr(L, "ps_render"):
+        L.ps_render.argtypes = [vp, vp, i32, i32, vp, i32, C.c_uint32, vp, vp, vp, vp, vp]
+        L.ps_render_list_stats.argtypes = [vp, vp, i32]
     _lib = L
     return L
 

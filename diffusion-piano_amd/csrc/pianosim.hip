@@ -7,6 +7,7 @@
 // entry points of include/pianosim.h. Descriptor -> device tables: model_build.h (host only).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <cmath>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,6 +19,7 @@
 
 #include "devmodel.h"
 #include "model_build.h"
+#include "render_build.h"
 #include "prims.h"
 #include "collide_x.h"
 
@@ -125,6 +127,16 @@ struct ps_env {
   // counts the calls that changed the set of per-env buffers (ps_set_augmentations, ps_record_midi,
   // ps_record_contacts): a snapshot lists the buffers of one generation (snapshot.inc)
   uint64_t row_gen;
+  // the ray caster (render.inc), all made by the handle's first ps_render: the hulls' face planes
+  // [NXT][HULL_MAXPLANE] float4 and their counts, the tile-list counter, and the scene scratch of
+  // r_rec_cap selected envs (no per-env state: not snapshot rows)
+  bool r_ready;
+  float* r_planes;
+  int* r_nplane;
+  unsigned long long* r_stat;
+  float* r_rec;
+  size_t r_rec_cap;
+  DevMem render_mem, render_rec_mem;
 };
 
 // Every entry point that touches device memory or launches binds the handle's device for its
@@ -147,6 +159,7 @@ struct DeviceGuard {
   if (!guard_.ok) return fail("hipSetDevice(" + std::to_string((E)->device) + ") failed")
 
 #include "snapshot.inc"
+#include "render.inc"
 
 // n elements device to device on the stream; a null caller pointer (dst or src) skips the copy
 template <class T>
@@ -179,8 +192,8 @@ extern "C" {
 
 const char* ps_last_error(void) { return g_err.c_str(); }
 // 4: ps_task_cfg.struct_size; 5: ps_task_cfg.hand_side; 6: ps_record_midi; 7: ps_task_cfg.observables;
-// 8: ps_snapshot_*
-int ps_version(void) { return 8; }
+// 8: ps_snapshot_*; 9: ps_render
+int ps_version(void) { return 9; }
 int ps_model_desc_size(void) { return (int)sizeof(ps_model_desc); }
 int ps_obs_dim(const ps_task_cfg* cfg) {
   std::string err;

@@ -98,7 +98,7 @@ class TaskConfig:
     initial_buffer_time: float = 0.0
     disable_fingering_reward: bool = False
     disable_forearm_reward: bool = False
-    disable_colorization: bool = False  # rendering only: no effect here
+    disable_colorization: bool = False  # render()'s default for `colorize` (fingertip and goal-key colours)
     disable_hand_collisions: bool = False
     energy_penalty_coef: float = 5e-3
     randomize_hand_positions: bool = False  # piano_with_shadow_hands.py:64,491-499
@@ -656,6 +656,16 @@ class BatchedPianoEnv:
             cur = getattr(self, name)
             cur.copy_(torch.where(ok.view(-1, *([1] * (cur.dim() - 1))), t.index_select(0, idx), cur))
 
+    # -- rendering (ps_render; rendering.py)
+    def render(self, camera="closeup", height: int = 240, width: int = 320, envs=None, depth: bool = False,
+               segmentation: bool = False, change_color_on_activation: bool = False, colorize: Optional[bool] = None):
+        """The envs ``envs`` (None: all N) ray-cast through ``camera`` (a name or index of
+        ``rendering.CAMERAS``, or a ``rendering.Camera``) on the current stream: one tensor, uint8
+        ``[n, H, W, 3]``, or float32 depth / int32 segmentation ``[n, H, W]`` (``rendering.render``)."""
+        from . import rendering
+        return rendering.render(self, camera, height, width, envs, depth, segmentation, change_color_on_activation,
+                                colorize)
+
     def obs_dict(self, obs=None) -> Dict[str, Any]:
         obs = self.obs if obs is None else obs
         return {k: obs[:, s] for k, s in self.obs_slices.items()}
@@ -840,6 +850,12 @@ class Environment:
     @property
     def core(self):
         return self._core
+
+    @property
+    def physics(self):
+        """``environment.physics``: ``physics.render(height, width, camera_id, depth, segmentation)``."""
+        from . import rendering
+        return rendering.Physics(self._core)
 
 
 DEBUG = ["RoboPianist-debug-TwinkleTwinkleLittleStar-v0"]

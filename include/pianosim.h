@@ -593,6 +593,85 @@ int ps_snapshot_save(ps_env* env, ps_snapshot* snap, void* stream);
 int ps_snapshot_restore(ps_env* env, const ps_snapshot* snap, const int32_t* src, int32_t* n_bad, void* stream);
 void ps_snapshot_destroy(ps_snapshot* snap);
 
+/* ---- rendering (ps_version 9): ray-cast cameras over the envs' analytic scene
+ * (physics.render(height, width, camera_id, depth, segmentation); the named cameras of
+ * models/piano/piano.py:100-141 are restated in rendering.py).
+ *
+ * The scene of an env is a function of its qpos row, its hand offset and (for the key colours) its
+ * t_idx and song tables: the hands' capsule, box and convex-hull colliders, the 88 key boxes each
+ * rotated about its hinge, the base box and a floor, the plane z = 0 (visual only, as the
+ * reference's stage). Unused collider slots, and with them the detached hand of the one-hand
+ * task, are not drawn. No meshes, textures, shadows, transparency or anti-aliasing.
+ *
+ * Camera: position, image right x and image up y (orthonormalised by the call, x first), vertical
+ * field of view in degrees; it looks along -z = -(x cross y). Row 0 of an image is its top. The
+ * ray of pixel (r, c) of an H x W image goes through the pixel's centre:
+ *   d = px x + py y - z,  py = (1 - 2 (r + 1/2) / H) tan(fovy / 2),
+ *                         px = (2 (c + 1/2) / W - 1) tan(fovy / 2) W / H.
+ * d is not normalised, so the parameter t of the first hit pos + t d is the depth along the
+ * optical axis (dm_control's depth). Only entering hits with t > 0 count (a camera inside an
+ * object does not see it); of two objects at the same t the lower id is drawn. A miss: depth +inf,
+ * segmentation -1, the background colour.
+ *
+ * Segmentation ids: global collider id g (capsule h * PS_HAND_NGEOM + i, then extra collider
+ * PS_NHAND * PS_HAND_NGEOM + h * PS_HAND_NXGEOM + i) 0 .. 63, key k PS_SEG_KEY0 + k, the base
+ * PS_SEG_BASE, the floor PS_SEG_FLOOR.
+ *
+ * Shading: a headlight at the camera. With n the unit outward normal at the hit and dhat = d / |d|,
+ *   rgb[k] = floor(255 clamp(colour[k] (PS_RENDER_AMBIENT + PS_RENDER_DIFFUSE max(0, -n . dhat)), 0, 1) + 1/2);
+ * a miss is the background colour unshaded. Colours (PS_RENDER_COLOR_*; piano_constants.py:83-85,
+ * piano.py:28, shadow_hand_constants.py:42-49): white key 0.9, black key 0.1, base 0.15, activated
+ * key (0.2, 0.8, 0.2), fingers th ff mf rf lf (0.8, 0.2, 0.8) (0.8, 0.2, 0.2) (0.2, 0.8, 0.8)
+ * (0.2, 0.2, 0.8) (0.8, 0.8, 0.2), hand 0.6, floor (0.2, 0.3, 0.4), background (0.05, 0.05, 0.1).
+ * PS_RENDER_ACTIVATION (change_color_on_activation): a key at activation (the task's rule:
+ * |clip(q, range) - range max| <= 0.5 degrees) takes the activation colour.
+ * PS_RENDER_COLORIZE (_colorize_fingertips / _colorize_keys): the colliders on a fingertip site's
+ * body (the distal links) take their finger's colour, and a key in the goal row of the step just
+ * played (row t_idx - 1; none right after a reset) that is not activated takes the colour of the
+ * finger the song tables assign to it (none for a song without fingering; the one-hand task: its
+ * hand's notes only).
+ * PS_RENDER_COUNT_LIST (diagnostic): every tile adds its culled list's length to a counter that
+ * ps_render_list_stats reads. */
+typedef struct {
+  double pos[3];
+  double x[3], y[3];
+  double fovy_deg;
+} ps_camera;
+#define PS_RENDER_ACTIVATION (1u << 0)
+#define PS_RENDER_COLORIZE (1u << 1)
+#define PS_RENDER_COUNT_LIST (1u << 16)
+#define PS_RENDER_ALL (PS_RENDER_ACTIVATION | PS_RENDER_COLORIZE | PS_RENDER_COUNT_LIST)
+#define PS_SEG_KEY0 64
+#define PS_SEG_BASE 152
+#define PS_SEG_FLOOR 153
+#define PS_RENDER_AMBIENT 0.3f
+#define PS_RENDER_DIFFUSE 0.7f
+#define PS_RENDER_COLOR_WHITE 0
+#define PS_RENDER_COLOR_BLACK 1
+#define PS_RENDER_COLOR_BASE 2
+#define PS_RENDER_COLOR_ACTIVATION 3
+#define PS_RENDER_COLOR_FINGER0 4 /* + finger: th ff mf rf lf */
+#define PS_RENDER_COLOR_HAND 9
+#define PS_RENDER_COLOR_FLOOR 10
+#define PS_RENDER_COLOR_BACKGROUND 11
+#define PS_RENDER_NCOLOR 12
+/* Renders the envs envs[0 .. n_sel) (device int32; repeats and any order allowed; NULL: all N envs
+ * in order, n_sel = N) through one camera into rgb u8 [n_sel][height][width][3], depth f32
+ * [n_sel][height][width] and seg i32 [n_sel][height][width] (device; any may be NULL, not all). An
+ * index outside [0, N) leaves its image untouched and adds one to *n_bad (device, may be NULL; the
+ * caller zeroes it). Asynchronous on the stream: a render after a step sees that step. It reads
+ * env memory and writes its outputs and a scratch of the handle (9792 B per selected env, grown to
+ * the largest n_sel so far) only. A handle's first call builds the hulls' face planes on the host
+ * (at most 96 per hull, else an error naming the hull) and allocates: init-time, not under stream
+ * capture; handles that never render allocate nothing. Refused with an error: width, height or
+ * n_sel <= 0, fovy outside (0, 180), a zero x or a y that is zero or parallel to x, all three
+ * outputs NULL, unknown flag bits. */
+int ps_render(ps_env* env, const ps_camera* cam, int width, int height, const int32_t* envs, int n_sel,
+              uint32_t flags, uint8_t* rgb, float* depth, int32_t* seg, int32_t* n_bad, void* stream);
+/* PS_RENDER_COUNT_LIST's counter (host memory; it synchronises): sum_tiles[0] the summed list
+ * lengths, [1] the tiles counted; reset != 0 zeroes it afterwards. */
+int ps_render_list_stats(ps_env* env, uint64_t* sum_tiles, int reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,7 +38,7 @@ awk '
   /^  - \.agpr_count:/ { k["agpr_count"] = $3 }
   /^amdhsa\.target:/ { if (name != "") emit(); name = "" }
   function emit() {
-    if (name !~ /pianosim_(queue_)?kernel/) return
+    if (name !~ /pianosim_(queue_)?kernel|render_(scene|rays)_kernel/) return
     printf "%s\tVGPRs: %s\tAGPRs: %s\tSGPRs: %s\tScratchSize [bytes/lane]: %s\tVGPR spills: %s\tSGPR spills: %s\tLDS Size [bytes/block]: %s\n",
       name, k["vgpr_count"] - k["agpr_count"], k["agpr_count"], k["sgpr_count"], k["private_segment_fixed_size"],
       k["vgpr_spill_count"], k["sgpr_spill_count"], k["group_segment_fixed_size"]
